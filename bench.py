@@ -2,6 +2,13 @@
 
   python bench.py --gpus N --steps K --warmup W        (N>1: one rank per GPU over RCCL — under torch.distributed.run, or, started
                                                         directly, bench.py spawns its N ranks itself: nemar_amd/launch.py)
+  python bench.py ... --dump-outputs DIR               also write what the last timed step computed as DIR/<name>.npy (dump_outputs)
+  python bench.py ... --full                           also run every side measurement listed below
+
+A plain run sets up, warms up, times K steps, writes its outputs if asked and prints the result line (the contract fields, the launch
+mode, peak memory of the timed region, per-rank step times).  Everything else — the roofline passes, the CPU baseline, the exact-route
+A/B, route agreement, the other BASELINE shapes, the grid_sample HBM-stress shape, the per-bucket all-reduce timing of N > 1 — runs only
+with --full, after the timed region (the CPU baseline before it); --no-cpu-baseline / --no-extras leave parts of it out.
 
 A step = one NEMARModel.optimize_parameters() (forward, discriminator update, translation+registration update, three
 fused Adam steps) on one synthetic batch already resident in HBM.  Workload = BASELINE.json configs[1]:
@@ -9,7 +16,7 @@ fused Adam steps) on one synthetic batch already resident in HBM.  Workload = BA
 (the reference default), lambda_smooth 10 — fp32 end to end (the reference's precision; no reduced-precision mode).
 N GPUs = N independent batch shards (weak scaling) + gradient all-reduce(avg) over RCCL.
 
-Prints ONE JSON line (rank 0) with the driver's contract fields plus
+Prints ONE JSON line (rank 0) with the driver's contract fields plus (roofline*, cpu_baseline: with --full only)
   roofline            dominant kernel = igemm_split16_kernel<2,2,3>: forward and data gradient of the 256->256 3x3 reflect
                       layers of the translation net's residual blocks (36 batch-16 launches per step, 17 % of the step), fp32
                       products as three fp16 partial products on the 16-bit MFMA.  achieved = algorithmic (fp32-equivalent) FLOP /
@@ -343,6 +350,81 @@ def route_agreement(dev):
     return out
 
 
+def roofline_pass(model, step, timer, dev):
+    """(--full) Per-launch durations of the roofline kernels: HIP events on the launch stream in a SEPARATE pass of two steps, after
+    the timed region (the event records would otherwise sit inside it).  Returns (ms, flop, launches) of that single-stream pass, the
+    same for the two-stream order (or None) and the peak memory of one single-stream step."""
+    import ctypes
+    from nemar_amd import _lib, ops
+    model._graph = None                  # the roofline pass needs eager launches (step parameters stay in device memory)
+    side_prev = ops.side_stream(False)   # ... on ONE stream: beside a side-stream kernel a launch shares the CUs and its duration says nothing about it
+    timer.enabled = True
+    lib = _lib.load()
+    lib.kernel_timer(1)
+    for _ in range(2):
+        step()
+    torch.cuda.synchronize()
+    timer.enabled = False
+    # peak memory of the single-stream order (the side-stream branch keeps the tensors it reads until the side stream has run it)
+    torch.cuda.reset_peak_memory_stats(dev)
+    step()
+    torch.cuda.synchronize()
+    peak_mem_single = torch.cuda.max_memory_allocated(dev)
+    ops.side_stream(side_prev)
+    tk_ms_c, tk_fl_c, tk_n_c = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+    lib.kernel_timer_read(ctypes.byref(tk_ms_c), ctypes.byref(tk_fl_c), ctypes.byref(tk_n_c))
+    lib.kernel_timer(0)
+    tk = (tk_ms_c.value, tk_fl_c.value, tk_n_c.value)
+    # ... and the same launches as the TIMED step runs them: beside the side stream's weight-gradient kernels (the data gradient's launches
+    # share the matrix pipe with them; the forward launches have the chip to themselves)
+    tk2 = None
+    if side_prev and tk[2]:
+        lib.kernel_timer(1)
+        for _ in range(2):
+            step()
+        torch.cuda.synchronize()
+        a_ms, a_fl, a_n = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
+        lib.kernel_timer_read(ctypes.byref(a_ms), ctypes.byref(a_fl), ctypes.byref(a_n))
+        lib.kernel_timer(0)
+        if a_n.value:
+            tk2 = (a_ms.value, a_fl.value, a_n.value)
+    return tk, tk2, peak_mem_single
+
+
+DUMP_BUDGET_BYTES = 63_000_000      # (64 MB in all with a margin for the .npy headers)
+DUMP_NET_ELEMS = 1 << 20         # per parameter / gradient vector (resnet_9blocks T alone has 11.4 M parameters)
+
+
+def dump_outputs(model, out_dir):
+    """What a caller of the timed step receives after its LAST step, as out_dir/<name>.npy: the losses (loss_<name>, float64), the
+    images the step computed (get_current_visuals() without the inputs real_*, float32) and each network's parameters and gradients
+    (<T|R|D>_params / <T|R|D>_grads, float32: the optimizer's flat buffers, alignment padding included).  An array above its share
+    of the 64 MB budget is replaced by a fixed, seeded sample of its flattened elements (sorted indices: the same for every run of the
+    same shapes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss_' + k: np.array([v], dtype=np.float64) for k, v in model.get_current_losses().items()}
+    nets = {}
+    for n in ('T', 'R', 'D'):
+        o = getattr(model, 'optimizer_' + n)          # ops.FlatAdam: every parameter / gradient is a view of these
+        nets[n + '_params'], nets[n + '_grads'] = o.flat_p, o.flat_g
+    vis = {k: v.detach() for k, v in model.get_current_visuals().items() if torch.is_tensor(v) and not k.startswith('real_')}
+    left = DUMP_BUDGET_BYTES - sum(a.nbytes for a in arrays.values()) - 4 * sum(min(t.numel(), DUMP_NET_ELEMS) for t in nets.values())
+    vis_elems = left // 4 // max(1, len(vis))
+
+    def host(t, cap):
+        a = t.float().cpu().numpy()
+        if a.size <= cap:
+            return a
+        idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+        return np.ascontiguousarray(a.reshape(-1)[idx])
+    arrays.update({k: host(t, vis_elems) for k, t in vis.items()})
+    arrays.update({k: host(t, DUMP_NET_ELEMS) for k, t in nets.items()})
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -350,14 +432,21 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--batch', type=int, default=8, help='per-GPU batch (weak scaling)')
     ap.add_argument('--size', type=int, default=256)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the side measurements: roofline passes, CPU baseline, exact-route A/B, route agreement, the other '
+                         'BASELINE shapes, grid_sample HBM stress, per-bucket all-reduce timing (N > 1)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (losses, computed images, parameters and gradients; seeded samples '
+                         'of the large ones, 64 MB at most) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
     ap.add_argument('--no-extras', action='store_true',
-                    help='skip the side measurements of the default run (exact-route A/B, the other BASELINE shapes, route agreement)')
+                    help='with --full: skip the side measurements (exact-route A/B, the other BASELINE shapes, route agreement)')
     ap.add_argument('--graph', choices=('auto', 'on', 'off'), default='auto',
                     help='replay the step as ONE captured hipGraph in the timed region (NEMARModel.enable_step_graph: every kernel of the '
                          'step, dropout offsets and Adam scalars in device memory; bit-identical to eager launches, tests/test_step_gpu.py). '
-                         'auto = on a single GPU, eager if the capture fails; the per-kernel roofline pass after the timed region is eager '
-                         'either way (event records cannot sit inside a graph)')
+                         'auto = on a single GPU whichever of the two a short pre-run probe measures faster, eager if the capture fails; '
+                         'the per-kernel roofline pass that --full runs after the timed region is eager either way (event records cannot '
+                         'sit inside a graph)')
     ap.add_argument('--opt', action='append', default=[], metavar='FLAG',
                     help='extra reference-style option for other BASELINE configs, e.g. --opt=--multi_resolution --opt=2')
     ap.add_argument('--ab-child', choices=('exact_route', 'route_agreement'), default=None, help=argparse.SUPPRESS)
@@ -389,7 +478,7 @@ def main():
     import contextlib
     import io
     cpu_base = None
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         # the CPU leg runs FIRST: the GPU phase is then one contiguous block at the end of the run (the driver samples GPU activity)
         with contextlib.redirect_stdout(sys.stderr):     # the net constructors print; stdout carries the JSON line only
             cpu_base = cpu_baseline()
@@ -443,6 +532,9 @@ def main():
                 step()
             torch.cuda.synchronize()
             return (time.perf_counter() - t) / n * 1e3
+        # the capture bound the visual attributes (fake_B, ...) to the tensors every replay writes; eager steps rebind them to fresh ones
+        # and a replay does not bind them back
+        captured = {n: model.__dict__[n] for n in model.visual_names if isinstance(n, str) and n in model.__dict__}
         t_graph = probe()
         g_saved, model._graph = model._graph, None           # (eager launches with the step parameters still in device memory)
         t_eager = probe()
@@ -454,6 +546,8 @@ def main():
             ops.pin_workspaces(False)
         else:
             model._graph = g_saved
+            model.__dict__.update(captured)
+        captured = None
 
     multi = dist.is_distributed()        # world > 1 (or the one-rank RCCL smoke configuration, NEMAR_DIST_SINGLE=1)
 
@@ -470,42 +564,11 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     peak_mem = torch.cuda.max_memory_allocated(dev)
-    # per-launch durations of the roofline kernels: HIP events on the launch stream in a SEPARATE pass of two steps, after
-    # the timed region (the event records would otherwise sit inside it)
-    model._graph = None                  # the roofline pass needs eager launches (step parameters stay in device memory)
-    side_prev = ops.side_stream(False)   # ... on ONE stream: beside a side-stream kernel a launch shares the CUs and its duration says nothing about it
-    timer.enabled = True
-    from nemar_amd import _lib
-    lib = _lib.load()
-    lib.kernel_timer(1)
-    for _ in range(2):
-        step()
-    torch.cuda.synchronize()
-    timer.enabled = False
-    # peak memory of the single-stream order (the side-stream branch keeps the tensors it reads until the side stream has run it)
-    torch.cuda.reset_peak_memory_stats(dev)
-    step()
-    torch.cuda.synchronize()
-    peak_mem_single = torch.cuda.max_memory_allocated(dev)
-    ops.side_stream(side_prev)
-    import ctypes
-    tk_ms_c, tk_fl_c, tk_n_c = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
-    lib.kernel_timer_read(ctypes.byref(tk_ms_c), ctypes.byref(tk_fl_c), ctypes.byref(tk_n_c))
-    lib.kernel_timer(0)
-    tk_ms, tk_flop, tk_n = tk_ms_c.value, tk_fl_c.value, tk_n_c.value
-    # ... and the same launches as the TIMED step runs them: beside the side stream's weight-gradient kernels (the data gradient's launches
-    # share the matrix pipe with them; the forward launches have the chip to themselves)
-    tk2 = None
-    if side_prev and tk_n:
-        lib.kernel_timer(1)
-        for _ in range(2):
-            step()
-        torch.cuda.synchronize()
-        a_ms, a_fl, a_n = ctypes.c_double(0.0), ctypes.c_double(0.0), ctypes.c_int(0)
-        lib.kernel_timer_read(ctypes.byref(a_ms), ctypes.byref(a_fl), ctypes.byref(a_n))
-        lib.kernel_timer(0)
-        if a_n.value:
-            tk2 = (a_ms.value, a_fl.value, a_n.value)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(model, a.dump_outputs)
+    tk_n, tk2, peak_mem_single = 0, None, None
+    if a.full:
+        (tk_ms, tk_flop, tk_n), tk2, peak_mem_single = roofline_pass(model, step, timer, dev)
     rank_ms = [dt / a.steps * 1e3]
     buckets = sum(len(getattr(model, n).launched) for n in ("sync_T", "sync_D", "sync_R"))
     if multi:
@@ -516,7 +579,7 @@ def main():
         dt = float(t.max().item())
     losses = model.get_current_losses()
     bucket_rows = []
-    if multi:
+    if multi and a.full:
         # one more step with events around every bucket's all-reduce (compute stream at launch, side stream at completion): achieved
         # bus bandwidth per bucket and how long finish() had to wait — the part of the exchange that is NOT hidden behind backward
         evs = []
@@ -544,8 +607,8 @@ def main():
                                 "ring_GBps_per_rank": nbytes * 2.0 * (world - 1) / world / max(ms, 1e-6) / 1e6})
     stn_cfg = opt.stn_cfg
     extras = {}
-    if world == 1 and not multi and not a.no_extras:
-        # side measurements of the default single-GPU run — after the timed region, never inside it
+    if a.full and world == 1 and not multi and not a.no_extras:
+        # side measurements of the single-GPU --full run — after the timed region, never inside it
         import gc
         ops.pin_workspaces(False)
         ops.step_params(False)
@@ -573,7 +636,7 @@ def main():
     spans = timer.summary()
     out = {
         "metric": "train images/sec (256x256 A/B pairs)", "value": a.batch * world * a.steps / dt,
-        "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "unit": "images/sec", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "full": a.full,
         "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32",
         "dtype_note": "fp32 tensors and fp32 accumulation throughout; convolutions with >= 5 output channels above 30 M multiply-adds form "
@@ -589,7 +652,7 @@ def main():
         "launch": "hipGraph replay" if graph_on else ("eager, weight-gradient branch on a side stream" + (" (%s)" % graph_note if graph_note else "")),
         "launch_probe": launch_probe,
         "losses_finite": all(v == v and abs(v) != float('inf') for v in losses.values()),
-        "peak_memory_GB": {"timed_region": peak_mem / 1e9, "single_stream_order": peak_mem_single / 1e9,
+        "peak_memory_GB": {"timed_region": peak_mem / 1e9, "single_stream_order": peak_mem_single / 1e9 if peak_mem_single is not None else None,
                            "note": "torch.cuda.max_memory_allocated; the weight-gradient branch on the side stream keeps the tensors it reads "
                                    "alive until the side stream has finished that branch (released per branch, nemar_amd/ops.py _on_side)"},
         "rank_ms_per_step": rank_ms,                      # one entry per rank: the N > 1 run cannot degrade to one rank unnoticed

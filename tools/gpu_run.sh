@@ -3,8 +3,8 @@
 #   tools/gpu_run.sh <out-name> <step> [<step> ...]
 # steps:
 #   test:<pytest -k expression>     pytest -m gpu subset (expression "all" = whole gpu tier)
-#   bench[:ENV=V,ENV=V]             python bench.py --no-cpu-baseline --no-extras under the given environment -> bench_<tag>.json
-#   fullbench                       python bench.py (the driver's line, cpu baseline and extras included)
+#   bench[:ENV=V,ENV=V]             python bench.py --full --no-cpu-baseline --no-extras under the given environment -> bench_<tag>.json
+#   fullbench                       python bench.py --full (the driver's line, cpu baseline and extras included)
 #   stats[:ENV=V,...]               rocprofv3 --kernel-trace --stats of 6 eager steps (NEMAR_SIDE_STREAM=0 unless given) -> kernel_stats_<tag>.csv
 #   layers                          tools/microbench_conv.py per-layer table
 #   py:<script.py args>             any tools/ script
@@ -22,13 +22,13 @@ for step in "$@"; do
       else timeout 1200 python -m pytest tests -m gpu -x -q -k "$arg" > $O/pytest_$tag.txt 2>&1; fi
       tail -15 $O/pytest_*.txt | tail -25 ;;
     bench)
-      env $envs timeout 900 python bench.py --no-cpu-baseline --no-extras --graph off > $O/bench_$tag.json 2> $O/bench_$tag.err
+      env $envs timeout 900 python bench.py --full --no-cpu-baseline --no-extras --graph off > $O/bench_$tag.json 2> $O/bench_$tag.err
       python -c "
 import json; d = json.load(open('$O/bench_$tag.json')); print('bench[%s]: %.2f img/s  %.2f ms/step  roofline %.3f (%.0f us)' % ('$arg', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline'].get('avg_launch_us', 0)))" || tail -5 $O/bench_$tag.err ;;
     fullbench)
-      timeout 1500 python bench.py > $O/bench_full.json 2> $O/bench_full.err; cut -c1-600 $O/bench_full.json ;;
+      timeout 1500 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; cut -c1-600 $O/bench_full.json ;;
     stats)
-      ( cd /tmp && export TMPDIR=/tmp && env NEMAR_SIDE_STREAM=0 $envs rocprofv3 --kernel-trace --stats -d $O/stats_$tag -- python $R/bench.py --steps 6 --warmup 2 --graph off --no-cpu-baseline --no-extras > $O/stats_line_$tag.json 2>/dev/null )
+      ( cd /tmp && export TMPDIR=/tmp && env NEMAR_SIDE_STREAM=0 $envs rocprofv3 --kernel-trace --stats -d $O/stats_$tag -- python $R/bench.py --full --steps 6 --warmup 2 --graph off --no-cpu-baseline --no-extras > $O/stats_line_$tag.json 2>/dev/null )
       python tools/prof_summary.py $O/stats_$tag $O/kernel_stats_$tag.csv > /dev/null 2>&1
       python - <<PY
 import csv

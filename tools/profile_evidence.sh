@@ -7,11 +7,11 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$1
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/bench.json 2> $O/bench.err
-rocprofv3 --kernel-trace --stats -d $O/stats -- python $R/bench.py --steps 6 --warmup 2 --graph off --no-cpu-baseline --no-extras > $O/bench_line_two_streams.json 2>/dev/null
+python $R/bench.py --full > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/stats -- python $R/bench.py --full --steps 6 --warmup 2 --graph off --no-cpu-baseline --no-extras > $O/bench_line_two_streams.json 2>/dev/null
 python $R/tools/prof_summary.py $O/stats $O/kernel_stats.csv > /dev/null 2>&1
 rm -rf $O/stats
-NEMAR_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats -d $O/stats1 -- python $R/bench.py --steps 6 --warmup 2 --graph off --no-cpu-baseline --no-extras > $O/bench_line_single_stream.json 2>/dev/null
+NEMAR_SIDE_STREAM=0 rocprofv3 --kernel-trace --stats -d $O/stats1 -- python $R/bench.py --full --steps 6 --warmup 2 --graph off --no-cpu-baseline --no-extras > $O/bench_line_single_stream.json 2>/dev/null
 python $R/tools/prof_summary.py $O/stats1 $O/kernel_stats_single_stream.csv > /dev/null 2>&1
 rm -rf $O/stats1
 G1="GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS"
