@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 602 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 603 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -311,6 +311,39 @@ int nemar_instnorm_bwd_planes(const float* x, const float* stats, const float* g
                               float* bias_partials, void* stream);
 /* gb[C] += sum over the batch of bias_partials [N, C], in batch order (bitwise reproducible) */
 int nemar_bias_from_partials(const float* bias_partials, int N, int C, float* gb, void* stream);
+/* ---- BatchNorm2d(C, affine=True, track_running_stats=True) (ABI 603) ---------------------------------------------------------
+ * nn.BatchNorm2d — reference models/networks.py:22 (`--norm batch`), the norm_layer of ResnetGenerator :351,358,373, ResnetBlock
+ * :426,439, UnetSkipConnectionBlock :517,519, NLayerDiscriminator :584,592 and PixelDiscriminator :626 — with the ReLU / LeakyReLU,
+ * Dropout and residual add that follow it fused in.  x, y, residual, gy, gx: [N, C, HW] fp32.  The N samples form `segments` equal
+ * segments: statistics, running-stat updates and gradient sums are per (segment, channel), the updates applied in segment order (what
+ * `segments` separate calls of the layer compute).  Every reduction has a fixed order: no floating-point atomics, bitwise reproducible.
+ *   train: mean, var = biased statistics of the segment, eps inside the sqrt;  y = [residual +] dropout(act(x * scale + shift)),
+ *          scale = weight * rstd, shift = bias - mean * scale;  saved[2, segments, C] = (mean | rstd);  running_mean / running_var
+ *          (nullable together) <- (1 - momentum) running + momentum (mean | var * M / (M - 1)) per segment in order, M = N / segments * HW
+ *          (> 1 required);  num_batches_tracked (nullable, int64) += segments.
+ *   eval:  the same apply with the running statistics (untouched); saved (nullable) [2, C] receives (running_mean | rstd) for the backward.
+ *   Dropout(p) (p = 0: none) is drawn exactly as nemar_dropout draws it over the [N, C, HW] tensor with (seed, offset) (+ the
+ *   nemar_set_dropout_base word).  max_words (nullable): NEMAR_MAX_WORDS(N) buffer, per-sample max |y| as nemar_instnorm_fwd_max.
+ *   bwd:   z = x * scale + shift recomputed, g = gy [* mask / (1 - p)] * act'(z), xhat = (x - mean) * rstd;
+ *          grad_weight[c] += sum g xhat, grad_bias[c] += sum g (nullable; summed over segments in order and ACCUMULATED);
+ *          gx (nullable) = scale * (g - sum g / M - xhat * sum(g xhat) / M) per segment (training), = scale * g (training == 0, with the
+ *          saved statistics of the eval forward).
+ * workspace: nemar_batchnorm_workspace(N, C, HW, segments) bytes. */
+size_t nemar_batchnorm_workspace(int N, int C, int HW, int segments);
+int nemar_batchnorm_fwd_train(const float* x, const float* residual, float* y, const float* weight, const float* bias,
+                              float* running_mean, float* running_var, long long* num_batches_tracked, float* saved,
+                              int N, int C, int HW, int segments, float eps, float momentum, int act, float slope,
+                              float dropout_p, unsigned long long seed, unsigned offset, void* max_words,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int nemar_batchnorm_fwd_eval(const float* x, const float* residual, float* y, const float* weight, const float* bias,
+                             const float* running_mean, const float* running_var, float* saved, int N, int C, int HW, float eps,
+                             int act, float slope, float dropout_p, unsigned long long seed, unsigned offset, void* max_words,
+                             void* stream);
+int nemar_batchnorm_bwd(const float* x, const float* gy, float* gx, const float* weight, const float* bias, const float* saved,
+                        float* grad_weight, float* grad_bias, int N, int C, int HW, int segments, int training, int act,
+                        float slope, float dropout_p, unsigned long long seed, unsigned offset, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* ---- K5/K6/K7: pointwise, pooling, resize, dropout -----------------------------------------------------------------
  * act_bwd: gx = gy * f'(.) expressed with the activation OUTPUT y (f fused into a conv epilogue):
  *     nn.LeakyReLU / nn.ReLU / nn.Tanh — reference models/networks.py:377,576 ; models/stn/layers.py:61-64. */

@@ -103,6 +103,11 @@ SIGNATURES = {
     "nemar_gan_loss_fwd": (_i, [_vp, _ll, _i, _i, _fl, _vp, _i, _vp, _sz, _vp]),
     "nemar_gan_loss_bwd": (_i, [_vp, _ll, _i, _i, _vp, _fl, _vp, _vp]),
     "nemar_adam_step": (_i, [_vp, _vp, _vp, _vp, _ll, _db, _db, _db, _db, _i, _vp]),
+    "nemar_batchnorm_workspace": (_sz, [_i, _i, _i, _i]),
+    "nemar_batchnorm_fwd_train": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _fl, _fl, _i, _fl, _fl, _u64, _u32,
+                                       _vp, _vp, _sz, _vp]),
+    "nemar_batchnorm_fwd_eval": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _fl, _i, _fl, _fl, _u64, _u32, _vp, _vp]),
+    "nemar_batchnorm_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _fl, _fl, _u64, _u32, _vp, _sz, _vp]),
 }
 
 

@@ -122,7 +122,8 @@ class BaseModel(ABC):
             torch.save(OrderedDict((k, v.detach().cpu().clone()) for k, v in net.state_dict().items()), path)
 
     def load_networks(self, epoch):
-        """Load '%s_net_%s.pth' (reference :180-203); tolerates `module.` prefixes and legacy InstanceNorm buffers."""
+        """Load '%s_net_%s.pth' (reference :180-203); tolerates `module.` prefixes and legacy InstanceNorm buffers;
+        BatchNorm networks keep their running statistics and counters."""
         for name, net in self._nets():
             path = os.path.join(self.save_dir, '%s_net_%s.pth' % (epoch, name))
             print('loading the model from %s' % path)
@@ -130,11 +131,12 @@ class BaseModel(ABC):
             if hasattr(state_dict, '_metadata'):
                 del state_dict._metadata
             clean = OrderedDict()
+            own = net.state_dict()
             for k, v in state_dict.items():
                 if k.startswith('module.'):
                     k = k[len('module.'):]
-                if k.endswith(('running_mean', 'running_var', 'num_batches_tracked')):
-                    continue            # InstanceNorm here has no buffers (affine=False, no running stats)
+                if k.endswith(('running_mean', 'running_var', 'num_batches_tracked')) and k not in own:
+                    continue            # InstanceNorm here has no buffers (affine=False, no running stats); BatchNorm keeps its own
                 clean[k] = v
             net.load_state_dict(clean)
 

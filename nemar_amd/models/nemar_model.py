@@ -98,12 +98,13 @@ class NEMARModel(BaseModel):
         self.train_stn = True
         self.setup_visualizers()
         self.tb_visualizer = None
-        # T's two applications and D's 3 + 2 applications per step run as single batches (valid without cross-sample ops, i.e. not
-        # with BatchNorm): the same graph with half the launches.  Round 1 measured no gain (78.15 vs 78.00 ms/step: every layer
+        # T's two applications and D's 3 + 2 applications per step run as single batches: the same graph with half the launches.  (With
+        # --norm batch the batched calls run under ops.norm_segments(k): BatchNorm takes its statistics and running-stat updates per
+        # segment of the batch, in segment order — those of the reference's k separate calls.)  Round 1 measured no gain (78.15 vs 78.00 ms/step: every layer
         # already filled the chip at batch 8); with the split-16 kernels, whose max / split / slab-sum passes are paid per launch,
         # it is 47.9 vs 50.2 ms/step on the same box, so it is the default.  NEMAR_BATCHED_PASSES=0 restores the reference's call
         # order (tests/test_step_gpu.py compares the two).
-        self._batched = opt.norm != 'batch' and os.environ.get('NEMAR_BATCHED_PASSES', '1') == '1'
+        self._batched = os.environ.get('NEMAR_BATCHED_PASSES', '1') == '1'
         # dropout masks: one Philox stream per process, governed by torch.manual_seed() and different on every rank
         ops.manual_seed(torch.initial_seed() + dist.rank())
         self.define_networks()
@@ -200,7 +201,8 @@ class NEMARModel(BaseModel):
             (f_a, f_b), f_reg = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 2)
             self.registered_real_A = self.netR.warp(f_a, [self.real_A])[0]
             # (only the second half is differentiated: the stem's data gradient runs on it alone)
-            both = self.netT(ops.grad_from(ops.cat_batch([self.real_A, self.registered_real_A]), n))
+            with ops.norm_segments(2):
+                both = self.netT(ops.grad_from(ops.cat_batch([self.real_A, self.registered_real_A]), n))
             self.fake_B, self.fake_TR_B = ops.split_batch(both, 2)
             self.fake_RT_B = self.netR.warp(f_b, [self.fake_B])[0]
             self.stn_reg_term = self.netR.regularization(f_reg, self.registered_real_A)
@@ -230,12 +232,14 @@ class NEMARModel(BaseModel):
         readers = 1 + len(self.netD_multiresolution)
         handles = [ops.fork(im, readers) for im in imgs]
         a_rep = ops.cat_batch([self.real_A] * k)
-        out = ops.split_batch(self.netD(a_rep, ops.cat_batch([h[0] for h in handles])), k)
+        with ops.norm_segments(k):
+            out = ops.split_batch(self.netD(a_rep, ops.cat_batch([h[0] for h in handles])), k)
         terms = [[self.criterionGAN(out[i], tr, w)] for i, (_, _, tr, w, _) in enumerate(specs)]
         for lvl, netD_S in enumerate(self.netD_multiresolution):
             a_r = self._half('real_A', self.real_A, lvl + 1)
             img_r = [self._half(name, h[lvl + 1], lvl + 1) for h, (_, name, _, _, det) in zip(handles, specs)]
-            out = ops.split_batch(netD_S(ops.cat_batch([a_r] * k), ops.cat_batch(img_r)), k)
+            with ops.norm_segments(k):
+                out = ops.split_batch(netD_S(ops.cat_batch([a_r] * k), ops.cat_batch(img_r)), k)
             for i, (_, _, tr, w, _) in enumerate(specs):
                 terms[i].append(self.criterionGAN(out[i], tr, w))
         return terms
@@ -316,6 +320,10 @@ class NEMARModel(BaseModel):
         # schedule an eager loop would follow, on untouched weights.  (The packed-weight images are rebuilt from the same values, so
         # the state the capture sees — T and R to be re-packed, D's forward images valid — is the steady state of every later step.)
         saved = [(o.m.clone(), o.v.clone(), o.step_count, o.param_groups[0]["lr"]) for o in opts]
+        # (--norm batch: the warm-up steps also move the running statistics and counters: put back as well)
+        bn_bufs = [b for net in (self.netT, self.netD, *self.netD_multiresolution) for name, b in net.named_buffers()
+                   if name.endswith(('running_mean', 'running_var', 'num_batches_tracked'))]
+        bn_saved = [b.clone() for b in bn_bufs]
         saved_step = ops._step_params["step"]
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
@@ -333,6 +341,8 @@ class NEMARModel(BaseModel):
                     o.v.copy_(v)
                     o.step_count = n
                     o.param_groups[0]["lr"] = lr
+                for b, v in zip(bn_bufs, bn_saved):
+                    b.copy_(v)
                 ops._step_params["step"] = saved_step
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()

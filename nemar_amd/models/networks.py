@@ -8,8 +8,11 @@ Appendix C), so checkpoints move in both directions.  The arithmetic is differen
 a call into the gfx950 kernel library (nemar_amd.ops) with padding, concatenation, bias, activation, InstanceNorm
 epilogues and residual adds fused — there is no nn.Conv2d / nn.InstanceNorm2d / F.* on the path.
 
-Only instance normalisation (the reference default, `--norm instance`) and `--norm none` have kernels; `batch`
-raises NotImplementedError (cross-sample statistics are outside the per-sample hot path).
+All three normalisations of the reference's `--norm` have kernels: instance (the default; per-sample statistics, fused into the
+producers' epilogues), none, and batch — nn.BatchNorm2d(affine=True, track_running_stats=True) as BatchNormParams (weight, bias and the
+running_mean / running_var / num_batches_tracked buffers under nn.BatchNorm2d's key names, at the reference's nn.Sequential positions)
+applied by ops.batch_norm (csrc/batchnorm.hip) with the activation, dropout and residual fused as for InstanceNorm.  BatchNorm statistics
+are per process (replica-local, as the reference's DataParallel); the registration networks keep their fixed InstanceNorm.
 """
 import math
 import os
@@ -38,6 +41,30 @@ class ConvParams(nn.Module):
         nn.init.uniform_(self.weight, -bound, bound)
         if self.bias is not None:
             nn.init.uniform_(self.bias, -bound, bound)
+
+
+class BatchNormParams(nn.Module):
+    """nn.BatchNorm2d(C, affine=True, track_running_stats=True)'s parameters and buffers under its key names (weight, bias,
+    running_mean, running_var, num_batches_tracked); calling it applies ops.batch_norm in the module's train / eval mode."""
+
+    def __init__(self, num_features, eps=1e-5, momentum=0.1):
+        super().__init__()
+        self.num_features, self.eps, self.momentum = num_features, eps, momentum
+        self.weight = nn.Parameter(torch.ones(num_features))
+        self.bias = nn.Parameter(torch.zeros(num_features))
+        self.register_buffer('running_mean', torch.zeros(num_features))
+        self.register_buffer('running_var', torch.ones(num_features))
+        self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
+
+    def forward(self, x, act=ops.ACT_NONE, slope=0.2, residual=None, dropout_p=0.0):
+        return ops.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, self.num_batches_tracked, self.training,
+                              act=act, slope=slope, residual=residual, eps=self.eps, momentum=self.momentum, dropout_p=dropout_p)
+
+
+def _bn_slot(slots, index, norm, channels):
+    """the reference's norm layer at nn.Sequential position `index`: a BatchNormParams for --norm batch, else nothing (InstanceNorm has
+    neither parameters nor buffers)"""
+    return slots.put(index, BatchNormParams(channels)) if norm == 'batch' else None
 
 
 class LinearParams(nn.Module):
@@ -74,14 +101,13 @@ class Slots(nn.Module):
 # helpers
 # ------------------------------------------------------------------------------------------------------
 def get_norm_layer(norm_type='instance'):
-    """Name of the normalisation the kernels will fuse: 'instance' | 'none'.  (reference :12-29)"""
+    """Name of the normalisation the kernels will fuse: 'batch' | 'instance' | None.  (reference :12-29)"""
+    if norm_type == 'batch':
+        return 'batch'
     if norm_type == 'instance':
         return 'instance'
     if norm_type == 'none':
         return None
-    if norm_type == 'batch':
-        raise NotImplementedError('normalization layer [batch] has no MI355X kernel on the NeMAR hot path; '
-                                  'use --norm instance (the reference default)')
     raise NotImplementedError('normalization layer [%s] is not found' % norm_type)
 
 
@@ -135,7 +161,7 @@ class PlateauLR:
 
 def init_weights(net, init_type='normal', init_gain=0.02):
     """(Re-)initialise every conv / linear weight of `net` (reference :62-96): normal | xavier | kaiming | orthogonal,
-    biases to zero."""
+    biases to zero; BatchNorm weights ~ N(1, init_gain), biases zero (running statistics untouched)."""
     if init_type not in ('normal', 'xavier', 'kaiming', 'orthogonal'):
         raise NotImplementedError('initialization method [%s] is not implemented' % init_type)
     for m in net.modules():
@@ -151,6 +177,9 @@ def init_weights(net, init_type='normal', init_gain=0.02):
                 nn.init.orthogonal_(w, gain=init_gain)
             if m.bias is not None:
                 nn.init.constant_(m.bias.data, 0.0)
+        elif isinstance(m, BatchNormParams):
+            nn.init.normal_(m.weight.data, 1.0, init_gain)
+            nn.init.constant_(m.bias.data, 0.0)
     ops.invalidate_packed_weights()      # .data writes do not bump tensor._version: drop every cached packed image
     print('initialize network with %s' % init_type)
 
@@ -235,6 +264,7 @@ class UnetSkipConnectionBlock(nn.Module):
         if input_nc is None:
             input_nc = outer_nc
         m = self.model = Slots()
+        down_bn = up_bn = None          # (--norm batch: the downnorm / upnorm layers, reference :517,519)
         if outermost:
             _ref(self, 'down', m.put(0, ConvParams(input_nc, inner_nc, 4, bias=use_bias)))
             _ref(self, 'sub', m.put(1, submodule))
@@ -243,10 +273,15 @@ class UnetSkipConnectionBlock(nn.Module):
             _ref(self, 'down', m.put(1, ConvParams(input_nc, inner_nc, 4, bias=use_bias)))
             object.__setattr__(self, 'sub', None)
             _ref(self, 'up', m.put(3, ConvParams(inner_nc, outer_nc, 4, bias=use_bias, transposed=True)))
+            up_bn = _bn_slot(m, 4, norm_layer, outer_nc)
         else:
             _ref(self, 'down', m.put(1, ConvParams(input_nc, inner_nc, 4, bias=use_bias)))
+            down_bn = _bn_slot(m, 2, norm_layer, inner_nc)
             _ref(self, 'sub', m.put(3, submodule))
             _ref(self, 'up', m.put(5, ConvParams(inner_nc * 2, outer_nc, 4, bias=use_bias, transposed=True)))
+            up_bn = _bn_slot(m, 6, norm_layer, outer_nc)
+        object.__setattr__(self, 'down_bn', down_bn)
+        object.__setattr__(self, 'up_bn', up_bn)
 
     def forward(self, a):
         """a: the block input (outermost) or LeakyReLU(block input) (otherwise)."""
@@ -259,11 +294,15 @@ class UnetSkipConnectionBlock(nn.Module):
         else:
             d = ops.conv2d(a, self.down.weight, self.down.bias, 2, 1, ops.PAD_ZERO,
                            act=ops.ACT_NONE if self.norm else ops.ACT_LRELU)
-            s = self.sub(_norm_act(d, self.norm, ops.ACT_LRELU))
+            s = self.sub(_norm_act(d, self.norm, ops.ACT_LRELU, bn=self.down_bn))
         u = ops.conv_transpose2d(s, self.up.weight, self.up.bias, 2, 1, 0, act=ops.ACT_NONE if self.norm else ops.ACT_RELU)
-        u = _norm_act(u, self.norm, ops.ACT_RELU)
-        if self.use_dropout:
-            u = ops.dropout(u, 0.5, self.training)      # commutes with the parent's ReLU (scale >= 0)
+        if self.up_bn is not None:
+            # (dropout fused into the BatchNorm pass: the same masks as ops.dropout would draw)
+            u = self.up_bn(u, act=ops.ACT_RELU, dropout_p=0.5 if (self.use_dropout and self.training) else 0.0)
+        else:
+            u = _norm_act(u, self.norm, ops.ACT_RELU)
+            if self.use_dropout:
+                u = ops.dropout(u, 0.5, self.training)      # commutes with the parent's ReLU (scale >= 0)
         return torch.cat([ops.activation(a, ops.ACT_RELU), u], 1)
 
 
@@ -287,9 +326,11 @@ class UnetGenerator(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------------------
-def _norm_act(x, norm, act, residual=None, planes=False, dropout_p=0.0):
-    """InstanceNorm + activation (+ dropout) (+ residual) as one kernel; with norm None the activation was already fused.
-    planes: the consumer is a 3x3 reflect-padded convolution (ops.instance_norm)."""
+def _norm_act(x, norm, act, residual=None, planes=False, dropout_p=0.0, bn=None):
+    """InstanceNorm / BatchNorm (`bn`: the layer's BatchNormParams) + activation (+ dropout) (+ residual) as one kernel; with norm None
+    the activation was already fused.  planes: the consumer is a 3x3 reflect-padded convolution (ops.instance_norm)."""
+    if norm == 'batch':
+        return bn(x, act=act, residual=residual, dropout_p=dropout_p)
     if norm == 'instance':
         return ops.instance_norm(x, act=act, residual=residual, planes=planes, dropout_p=dropout_p)
     if dropout_p > 0.0:
@@ -314,8 +355,10 @@ class ResnetBlock(nn.Module):
         self.conv_block = Slots()
         first = 1 if padding_type == 'reflect' else 0
         _ref(self, 'c1', self.conv_block.put(first, ConvParams(dim, dim, 3, bias=use_bias)))
+        object.__setattr__(self, 'bn1', _bn_slot(self.conv_block, first + 1, norm_layer, dim))
         second = first + 2 + (1 if use_dropout else 0) + (2 if padding_type == 'reflect' else 1)
         _ref(self, 'c2', self.conv_block.put(second, ConvParams(dim, dim, 3, bias=use_bias)))
+        object.__setattr__(self, 'bn2', _bn_slot(self.conv_block, second + 1, norm_layer, dim))
 
     def forward(self, x):
         fused_act = ops.ACT_NONE if self.norm else ops.ACT_RELU
@@ -330,10 +373,11 @@ class ResnetBlock(nn.Module):
         # the block's input feeds conv1 and the skip: the skip's gradient is added in the last pass of conv1's data gradient
         h, x_skip = ops.conv2d_with_skip(x, self.c1.weight, self.c1.bias, 1, 1, self.pad_mode, act=fused_act)
         # (norm + ReLU + Dropout in one pass; where conv2 runs on the fp16 x 3 route its operand planes come out of the same pass)
-        h = _norm_act(h, self.norm, ops.ACT_RELU, planes=reflect, dropout_p=0.5 if (self.use_dropout and self.training) else 0.0)
+        h = _norm_act(h, self.norm, ops.ACT_RELU, planes=reflect, dropout_p=0.5 if (self.use_dropout and self.training) else 0.0,
+                      bn=self.bn1)
         h = ops.conv2d(h, self.c2.weight, self.c2.bias, 1, 1, self.pad_mode)
         if self.norm:
-            return _norm_act(h, self.norm, ops.ACT_NONE, residual=x_skip, planes=reflect and self.feeds_block)
+            return _norm_act(h, self.norm, ops.ACT_NONE, residual=x_skip, planes=reflect and self.feeds_block, bn=self.bn2)
         return x_skip + h
 
 
@@ -350,11 +394,13 @@ class ResnetGenerator(nn.Module):
         m = self.model = Slots()
         idx = 1
         _ref(self, 'stem', m.put(idx, ConvParams(input_nc, ngf, 7, bias=use_bias)))
+        self.bn = [_bn_slot(m, idx + 1, norm_layer, ngf)]         # (--norm batch: stem, down x 2, up x 2)
         idx += per
         self.down = []
         for i in range(2):
             mult = 2 ** i
             self.down.append(m.put(idx, ConvParams(ngf * mult, ngf * mult * 2, 3, bias=use_bias)))
+            self.bn.append(_bn_slot(m, idx + 1, norm_layer, ngf * mult * 2))
             idx += per
         self.blocks = []
         for _ in range(n_blocks):
@@ -367,6 +413,7 @@ class ResnetGenerator(nn.Module):
         for i in range(2):
             mult = 2 ** (2 - i)
             self.up.append(m.put(idx, ConvParams(ngf * mult, ngf * mult // 2, 3, bias=use_bias, transposed=True)))
+            self.bn.append(_bn_slot(m, idx + 1, norm_layer, ngf * mult // 2))
             idx += per
         idx += 1                               # the ReflectionPad2d(3) before the head
         _ref(self, 'head', m.put(idx, ConvParams(ngf, output_nc, 7, bias=True)))
@@ -374,15 +421,16 @@ class ResnetGenerator(nn.Module):
     def forward(self, x):
         a = ops.ACT_NONE if self.norm else ops.ACT_RELU
         h = ops.conv2d(x, self.stem.weight, self.stem.bias, 1, 3, ops.PAD_REFLECT, act=a)
-        h = _norm_act(h, self.norm, ops.ACT_RELU)
+        h = _norm_act(h, self.norm, ops.ACT_RELU, bn=self.bn[0])
         for i, c in enumerate(self.down):
             h = ops.conv2d(h, c.weight, c.bias, 2, 1, ops.PAD_ZERO, act=a)
-            h = _norm_act(h, self.norm, ops.ACT_RELU, planes=self.reflect_blocks and self.n_blocks > 0 and i == len(self.down) - 1)
+            h = _norm_act(h, self.norm, ops.ACT_RELU, planes=self.reflect_blocks and self.n_blocks > 0 and i == len(self.down) - 1,
+                          bn=self.bn[1 + i])
         for b in self.blocks:
             h = b(h)
-        for c in self.up:
+        for i, c in enumerate(self.up):
             h = ops.conv_transpose2d(h, c.weight, c.bias, 2, 1, 1, act=a)
-            h = _norm_act(h, self.norm, ops.ACT_RELU)
+            h = _norm_act(h, self.norm, ops.ACT_RELU, bn=self.bn[3 + i])
         return ops.conv2d(h, self.head.weight, self.head.bias, 1, 3, ops.PAD_REFLECT, act=ops.ACT_TANH)
 
     def init_to_identity(self):
@@ -399,17 +447,21 @@ class NLayerDiscriminator(nn.Module):
         self.norm = norm_layer
         per = 3 if norm_layer else 2
         m = self.model = Slots()
-        self.layers = []                      # (params, stride)
+        self.layers = []                      # (params, stride, normed)
+        self.bn = []                          # (--norm batch: the BatchNormParams of each normed layer, else None)
         idx = 0
         self.layers.append((m.put(idx, ConvParams(input_nc, ndf, 4, bias=True)), 2, False))
+        self.bn.append(None)
         idx += 2
         nf = 1
         for n in range(1, n_layers):
             prev, nf = nf, min(2 ** n, 8)
             self.layers.append((m.put(idx, ConvParams(ndf * prev, ndf * nf, 4, bias=use_bias)), 2, True))
+            self.bn.append(_bn_slot(m, idx + 1, norm_layer, ndf * nf))
             idx += per
         prev, nf = nf, min(2 ** n_layers, 8)
         self.layers.append((m.put(idx, ConvParams(ndf * prev, ndf * nf, 4, bias=use_bias)), 1, True))
+        self.bn.append(_bn_slot(m, idx + 1, norm_layer, ndf * nf))
         idx += per
         _ref(self, 'final', m.put(idx, ConvParams(ndf * nf, 1, 4, bias=True)))
         # Schedule hint (ops._Conv2d backward): D's backward chain is short (four data gradients) and its weight gradients long (the 4x4
@@ -428,7 +480,8 @@ class NLayerDiscriminator(nn.Module):
             h = ops.conv2d(h, c.weight, c.bias, stride, 1, ops.PAD_ZERO, act=fuse, slope=0.2,
                            x2=x2 if i == 0 else None)
             if normed and self.norm:
-                h = ops.instance_norm(h, act=ops.ACT_LRELU, slope=0.2)
+                h = _norm_act(h, self.norm, ops.ACT_LRELU, bn=self.bn[i]) if self.norm == 'batch' else \
+                    ops.instance_norm(h, act=ops.ACT_LRELU, slope=0.2)
         return ops.conv2d(h, self.final.weight, self.final.bias, 1, 1, ops.PAD_ZERO)
 
 
@@ -442,13 +495,14 @@ class PixelDiscriminator(nn.Module):
         n = self.net = Slots()
         _ref(self, 'c0', n.put(0, ConvParams(input_nc, ndf, 1, bias=True)))
         _ref(self, 'c1', n.put(2, ConvParams(ndf, ndf * 2, 1, bias=use_bias)))
+        object.__setattr__(self, 'bn1', _bn_slot(n, 3, norm_layer, ndf * 2))
         _ref(self, 'c2', n.put(5 if norm_layer else 4, ConvParams(ndf * 2, 1, 1, bias=use_bias)))
 
     def forward(self, x, x2=None):
         h = ops.conv2d(x, self.c0.weight, self.c0.bias, act=ops.ACT_LRELU, x2=x2)
         if self.norm:
             h = ops.conv2d(h, self.c1.weight, self.c1.bias)
-            h = ops.instance_norm(h, act=ops.ACT_LRELU)
+            h = self.bn1(h, act=ops.ACT_LRELU) if self.bn1 is not None else ops.instance_norm(h, act=ops.ACT_LRELU)
         else:
             h = ops.conv2d(h, self.c1.weight, self.c1.bias, act=ops.ACT_LRELU)
         return ops.conv2d(h, self.c2.weight, self.c2.bias)

@@ -997,6 +997,96 @@ def instance_norm(x, act=ACT_NONE, slope=0.2, residual=None, eps=1e-5, planes=Fa
     return _InstanceNorm.apply(x, residual, act, slope, eps, bool(planes), float(dropout_p))
 
 
+# ---- BatchNorm2d(affine=True, track_running_stats=True) (csrc/batchnorm.hip) --------------------------------------------------------------
+# The model's batched passes run one network over k stacked batches (T over [a ; R(a)], D over [real ; fakes]); BatchNorm's statistics must
+# then stay those of the reference's k separate calls.  `with norm_segments(k):` around such a call makes every batch_norm inside it take
+# statistics, running-stat updates and gradient sums per segment of N / k samples, the updates in segment order.
+_norm_segments = [1]
+
+
+@contextlib.contextmanager
+def norm_segments(k):
+    prev = _norm_segments[0]
+    _norm_segments[0] = int(k)
+    try:
+        yield
+    finally:
+        _norm_segments[0] = prev
+
+
+class _BatchNorm(Function):
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, num_batches_tracked, training, act, slope, eps, momentum,
+                drop_p, segments):
+        x, residual = _c(x), _c(residual)
+        N, C, H, W = x.shape
+        HW = H * W
+        S = int(segments) if training else 1
+        if N % S:
+            raise ValueError("batch_norm: %d segments do not divide a batch of %d" % (S, N))
+        if training and (N // S) * HW == 1:
+            raise ValueError("Expected more than 1 value per channel when training, got input size %s" % (list(x.shape),))
+        y = torch.empty_like(x)
+        ctx.drop = None
+        seed = off = 0
+        if drop_p > 0.0:
+            _dropout_state["offset"] = (_dropout_state["offset"] + 1) & 0xFFFFFFFF
+            seed, off = _dropout_state["seed"], _dropout_state["offset"]
+            ctx.drop = (drop_p, seed, off)
+        P = (HW + 1023) // 1024
+        words = _max_words(N, x.device) if (_wants_max(x) and (C * P + 3) // 4 <= MAX_PARTIALS) else None
+        saved = torch.empty((2, S, C), dtype=torch.float32, device=x.device)
+        if training:
+            wsb = Q.batchnorm_workspace(N, C, HW, S)
+            L.batchnorm_fwd_train(_p(x), _p(residual), _p(y), _p(weight), _p(bias), _p(running_mean), _p(running_var),
+                                  _p(num_batches_tracked), _p(saved), N, C, HW, S, eps, momentum, act, slope, drop_p, seed, off,
+                                  _p(words), _p(_workspace(wsb, x.device)), wsb, _stream())
+        else:
+            L.batchnorm_fwd_eval(_p(x), _p(residual), _p(y), _p(weight), _p(bias), _p(running_mean), _p(running_var), _p(saved),
+                                 N, C, HW, eps, act, slope, drop_p, seed, off, _p(words), _stream())
+        if words is not None:
+            _tag_max(y, words)
+        ctx.save_for_backward(x, saved, weight, bias)
+        ctx.weight, ctx.bias = weight, bias
+        _note_use(weight)
+        _note_use(bias)
+        ctx.cfg = (S, bool(training), act, slope)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, saved, w, b = ctx.saved_tensors
+        S, training, act, slope = ctx.cfg
+        gy = _c(gy)
+        N, C, H, W = x.shape
+        need_x, need_res, need_w, need_b = ctx.needs_input_grad[:4]
+        gx = torch.empty_like(x) if need_x else None
+        gw = _grad_buffer(ctx.weight) if need_w else None
+        gb = _grad_buffer(ctx.bias) if need_b else None
+        if gx is not None or gw is not None or gb is not None:
+            p, seed, off = ctx.drop if ctx.drop is not None else (0.0, 0, 0)
+            wsb = Q.batchnorm_workspace(N, C, H * W, S)
+            L.batchnorm_bwd(_p(x), _p(gy), _p(gx), _p(w), _p(b), _p(saved), _p(gw), _p(gb), N, C, H * W, S, int(training), act, slope,
+                            p, seed, off, _p(_workspace(wsb, x.device)), wsb, _stream())
+        if gw is not None:
+            grad_ready(ctx.weight)
+        if gb is not None:
+            grad_ready(ctx.bias)
+        return gx, (gy if need_res else None), None, None, None, None, None, None, None, None, None, None, None, None
+
+
+def batch_norm(x, weight, bias, running_mean, running_var, num_batches_tracked, training, act=ACT_NONE, slope=0.2, residual=None, eps=1e-5,
+               momentum=0.1, dropout_p=0.0):
+    """(residual +) dropout(act(BatchNorm2d(x))) with affine=True, track_running_stats=True.  Training: batch statistics (per segment
+    of the enclosing norm_segments(k)); the running statistics and the counter are updated on the device, also under torch.no_grad(), as
+    nn.BatchNorm2d does.  Eval: the running statistics, left untouched.  weight / bias gradients accumulate into their .grad."""
+    if running_mean.dtype != torch.float32 or running_var.dtype != torch.float32 or num_batches_tracked.dtype != torch.int64:
+        raise TypeError("batch_norm: running statistics must be fp32 and the counter int64")
+    return _BatchNorm.apply(x, residual, weight, bias, running_mean, running_var, num_batches_tracked, bool(training), act, slope, float(eps),
+                            float(momentum), float(dropout_p), _norm_segments[0])
+
+
 # ---- one ResnetBlock of the wide route as ONE autograd node (round 6) -------------------------------------------------------------------
 # x + IN(conv3x3(reflect(drop(relu(IN(conv3x3(reflect(x)))))))) — reference models/networks.py:418-446.  As separate nodes the backward pass of
 # a block costs, besides its four matrix-pipe kernels: two InstanceNorm backward passes that write fp32 gradients, two split passes that
