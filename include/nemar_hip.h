@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 603 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 604 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -396,6 +396,33 @@ int nemar_adam_step_dev(float* p, const float* g, float* m, float* v, long long 
  * (pool index, y0, x0, flip), 16-byte aligned; y [B,C,Hc,Wc] = (pool[...] * scale - 0.5) / 0.5. */
 int nemar_crop_flip_normalize(const float* pool, const int* params, float* y, int M, int B, int C, int H, int W,
                               int Hc, int Wc, float scale, void* stream);
+
+/* Known-misalignment training pairs and the registration-error meter (not in the reference, whose data sets come misaligned: here the
+ * pipeline deforms modality A by a seeded smooth transformation and carries its ground truth with the batch).
+ * Conventions: pixel coordinates q = (x, y), integer values at pixel centres, origin at the top-left pixel of the output crop
+ * [Hc,Wc]; a ground-truth field g is [B,2,Hc,Wc] IN PIXELS, channel 0 = x (the UNet STN's order); the deformed image is
+ * A'(q) = A_crop(q + g(q)).  Tensors of any alignment and odd widths are served (one pixel per lane instead of 16-byte accesses).
+ *
+ * nemar_deform_field: g from params [B, 6 + 2*gh*gw] (device): a11 a12 tx a21 a22 ty, an affine map about the crop centre
+ * c = ((Wc-1)/2, (Hc-1)/2) whose displacement is (M - I)(q - c) + t, then a control lattice [2,gh,gw] of displacements in pixels
+ * interpolated over the crop by a uniform cubic B-spline (gh, gw >= 4: its gh-3 x gw-3 segments span the crop; gh = gw = 0: no
+ * lattice) and added to the affine displacement. */
+int nemar_deform_field(const float* params, float* g, int B, int Hc, int Wc, int gh, int gw, void* stream);
+/* nemar_crop_flip_normalize (same pool, params [B,4], scale) with every output pixel q read bilinearly from the cropped-and-flipped
+ * image at q + g(q), the position clamped to the crop window (border padding).  g == 0 gives nemar_crop_flip_normalize's output bit
+ * for bit. */
+int nemar_crop_flip_deform_normalize(const float* pool, const int* params, const float* g, float* y, int M, int B, int C,
+                                     int H, int W, int Hc, int Wc, float scale, void* stream);
+/* The meter.  pred is the STN's prediction as nemar_grid_sample_fwd takes it: NEMAR_GRID_UNET offsets [N,2,H,W] or NEMAR_GRID_AFFINE
+ * dtheta [N,6].  S(x) = the pixel position that kernel samples for output pixel x; the registered image is A'(S(x)) =
+ * A(S(x) + g(S(x))), so the residual is r(x) = S(x) + g(S(x)) - x, g read bilinearly at S(x); |.| is the Euclidean length.
+ * out [N,6] per sample, SUMS (the caller divides): valid_count (S(x) inside [0,W-1] x [0,H-1]), sum |r| over valid pixels,
+ * max |r| over valid pixels, sum |g(x)| over all pixels (the error before registration), fold_count (determinant of the forward-
+ * difference Jacobian of x -> S(x) <= 0), interior_count (pixels that have both forward neighbours).  Per-workgroup partials merged in
+ * a fixed order: bitwise repeatable.  A workspace smaller than nemar_registration_error_workspace() bytes is NEMAR_EINVAL. */
+size_t nemar_registration_error_workspace(int N, int H, int W);
+int nemar_registration_error(const float* pred, int grid_mode, const float* g, float* out, void* workspace, size_t ws_bytes,
+                             int N, int H, int W, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

@@ -13,31 +13,17 @@
 // offset loads and output stores are 16 B/lane coalesced when Wo % 4 == 0; the four-corner gathers hit
 // L1/L2 (each source texel is touched by ~4 neighbouring lanes in the near-identity regime).
 #include "common.h"
+#include "warp_grid.h"   // grid modes, linspace / affine base, make_grid, sample_position (shared with deform.hip)
 
 namespace {
-
-constexpr int GRID_EXPLICIT = 0;  // grid [N,Ho,Wo,2]  (x,y) interleaved, normalised coords
-constexpr int GRID_UNET = 1;      // offsets [N,2,Ho,Wo] planar; + linspace(-1,1) identity (ch0 = x)
-constexpr int GRID_AFFINE = 2;    // dtheta [N,6]; theta = dtheta + [1,0,0,0,1,0]; affine_grid(align_corners=False)
-
-// torch.linspace(-1, 1, n)[i] in fp32: fused multiply-add from the nearer end (ATen RangeFactories
-// symmetric form; bit-exact against torch CPU, see tests/test_oracle_torch.py)
-__device__ __forceinline__ float linspace_m1_p1(int i, int n) {
-    if (n <= 1) return -1.f;
-    const float step = 2.f / (float)(n - 1);
-    return (i < n / 2) ? fmaf(step, (float)i, -1.f) : fmaf(-step, (float)(n - 1 - i), 1.f);
-}
-// affine_grid base coordinate, align_corners=False: (2i+1)/n - 1
-__device__ __forceinline__ float affine_base(int i, int n) { return (2.f * (float)i + 1.f) / (float)n - 1.f; }
 
 struct Sample {
     int x0, y0;
     float tx, ty;  // ix - x0, iy - y0
 };
 __device__ __forceinline__ Sample locate(float gx, float gy, int W, int H) {
-    // unnormalise, align_corners=False: ((g + 1) * size - 1) / 2
-    const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
-    const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+    float ix, iy;
+    sample_position(gx, gy, W, H, ix, iy);
     const float fx = floorf(ix), fy = floorf(iy);
     Sample s;
     // clamp far-out-of-range coordinates before the int conversion (all four corners are OOB anyway)
@@ -46,25 +32,6 @@ __device__ __forceinline__ Sample locate(float gx, float gy, int W, int H) {
     s.tx = ix - fx;
     s.ty = iy - fy;
     return s;
-}
-
-template <int MODE>
-__device__ __forceinline__ void make_grid(const float* __restrict__ gsrc, int n, int h, int w, int Ho, int Wo,
-                                          const float* th, float& gx, float& gy) {
-    if (MODE == GRID_EXPLICIT) {
-        const float2 g = *reinterpret_cast<const float2*>(gsrc + (((size_t)n * Ho + h) * Wo + w) * 2);
-        gx = g.x;
-        gy = g.y;
-    } else if (MODE == GRID_UNET) {
-        const size_t plane = (size_t)Ho * Wo;
-        const size_t o = (size_t)n * 2 * plane + (size_t)h * Wo + w;
-        gx = linspace_m1_p1(w, Wo) + gsrc[o];
-        gy = linspace_m1_p1(h, Ho) + gsrc[o + plane];
-    } else {
-        const float xb = affine_base(w, Wo), yb = affine_base(h, Ho);
-        gx = th[0] * xb + th[1] * yb + th[2];
-        gy = th[3] * xb + th[4] * yb + th[5];
-    }
 }
 
 // ---- forward ---------------------------------------------------------------------------------------
@@ -78,8 +45,7 @@ __global__ __launch_bounds__(256) void grid_sample_fwd_kernel(const float* __res
     const int items = Ho * wq;
     float th[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (MODE == GRID_AFFINE) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) th[i] = gsrc[n * 6 + i] + ((i == 0 || i == 4) ? 1.f : 0.f);
+        affine_theta(gsrc, n, th);
     }
     const float* inN = in + (size_t)n * C * H * W;
     float* outN = out + (size_t)n * C * Ho * Wo;
@@ -164,8 +130,7 @@ __global__ __launch_bounds__(256) void grid_sample_bwd_kernel(const float* __res
     const int items = Ho * Wo;
     float th[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (MODE == GRID_AFFINE) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) th[i] = gsrc[n * 6 + i] + ((i == 0 || i == 4) ? 1.f : 0.f);
+        affine_theta(gsrc, n, th);
     }
     const float* inN = in + (size_t)n * C * H * W;
     float* ginN = NEED_GIN ? gin + (size_t)n * C * H * W : nullptr;
@@ -250,8 +215,7 @@ __global__ __launch_bounds__(TL_THREADS) void grid_sample_bwd_tiled_kernel(const
     const int rx0 = x0 - TL_HALO, ry0 = y0 - TL_HALO;          // region origin in input coordinates
     float th[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (MODE == GRID_AFFINE) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) th[i] = gsrc[n * 6 + i] + ((i == 0 || i == 4) ? 1.f : 0.f);
+        affine_theta(gsrc, n, th);
     }
     const size_t plane = (size_t)H * W;
     const float* inN = in + (size_t)n * C * plane;
@@ -470,8 +434,7 @@ __global__ __launch_bounds__(GT_THREADS) void grid_sample_bwd_gather_kernel(cons
     const int tid = threadIdx.x;
     float th[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (MODE == GRID_AFFINE) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) th[i] = gsrc[n * 6 + i] + ((i == 0 || i == 4) ? 1.f : 0.f);
+        affine_theta(gsrc, n, th);
     }
     const size_t plane = (size_t)H * W;
     const float* inN = in + (size_t)n * C * plane;

@@ -16,8 +16,17 @@ flip, and Normalize((0.5,)*3, (0.5,)*3) (reference :81-112) happen in the kernel
                         default --img_height 288 --img_width 384
 The resize is a function of the image alone (the reference recomputes the same bicubic resize every epoch), so it is applied ONCE,
 when the pool is brought into HBM (bicubic, antialiased, clamped to [0, 1] — the reference's PIL resize works on clamped 8-bit
-values); per batch only the crop / flip / normalise launch runs."""
+values); per batch only the crop / flip / normalise launch runs.
+
+`--misalign affine|elastic|both` (default none: aligned pairs, as above) turns the aligned pool into KNOWN-MISALIGNMENT training pairs: per
+pair a smooth transformation is drawn on the host from a random stream of its own (the crop / flip sequence of a seed does not change),
+its field g [B,2,Hc,Wc] — pixels, channel 0 = x, A'(q) = A_crop(q + g(q)) — is built on the device (nemar_deform_field: affine about the
+crop centre + cubic B-spline lattice) and modality A is cropped, flipped AND deformed by one launch (nemar_crop_flip_deform_normalize,
+border-clamped bilinear); B takes the plain launch.  The batch then carries 'gt_field', which the model's registration-error meter reads
+(util/visualizer.RegistrationMeter).  `--synthetic_pairs mapped` makes the synthetic pool registrable: A is a band-limited random texture,
+B a fixed per-channel non-linear remap of it (the default `independent` pools share nothing)."""
 import ctypes
+import math
 import os
 import random
 
@@ -33,6 +42,14 @@ class GpuPairsDataset(BaseDataset):
     def modify_commandline_options(parser, is_train):
         parser.add_argument('--pool_size_pairs', type=int, default=64, help='synthetic pool: number of A/B pairs')
         parser.add_argument('--data_seed', type=int, default=1234)
+        parser.add_argument('--misalign', type=str, default='none', choices=('none', 'affine', 'elastic', 'both'),
+                            help='deform modality A by a known, seeded smooth transformation and return its field as gt_field')
+        parser.add_argument('--misalign_max_px', type=float, default=8.0, help='largest translation and largest lattice displacement, pixels')
+        parser.add_argument('--misalign_rot_deg', type=float, default=5.0, help='rotation drawn in +- this many degrees')
+        parser.add_argument('--misalign_scale', type=float, default=0.05, help='scale drawn in 1 +- this')
+        parser.add_argument('--misalign_grid', type=int, default=6, help='control points per side of the elastic lattice (>= 4)')
+        parser.add_argument('--synthetic_pairs', type=str, default='independent', choices=('independent', 'mapped'),
+                            help='synthetic pool: two independent noise pools, or a band-limited texture and a non-linear remap of it')
         return parser
 
     def __init__(self, opt):
@@ -40,6 +57,14 @@ class GpuPairsDataset(BaseDataset):
         self.device = torch.device('cuda', opt.gpu_ids[0]) if opt.gpu_ids else torch.device('cuda')
         # crop positions / flips: one stream per rank (every rank augments its own samples)
         self.rng = random.Random(getattr(opt, 'data_seed', 1234) + 7919 * int(getattr(opt, 'shard_rank', 0)))
+        # the misalignment parameters: a stream of their own, so that turning --misalign on leaves the crops and flips of a seed as they are
+        self.misalign = getattr(opt, 'misalign', 'none')
+        if self.misalign not in ('none', 'affine', 'elastic', 'both'):
+            raise ValueError('--misalign %s is not one of none, affine, elastic, both' % self.misalign)
+        self.rng_misalign = random.Random((getattr(opt, 'data_seed', 1234) + 7919 * int(getattr(opt, 'shard_rank', 0))) * 1000003 + 604)
+        self.lattice = int(getattr(opt, 'misalign_grid', 6)) if self.misalign in ('elastic', 'both') else 0
+        if self.misalign in ('elastic', 'both') and self.lattice < 4:
+            raise ValueError('--misalign_grid %d: a cubic B-spline lattice needs at least 4 control points per side' % self.lattice)
         self.pre = getattr(opt, 'preprocess', 'resize_and_crop')
         if self.pre not in ('resize_and_crop', 'crop', 'scale_width', 'scale_width_and_crop', 'none'):
             raise ValueError('--preprocess %s is not one of the reference\'s modes' % self.pre)
@@ -51,8 +76,12 @@ class GpuPairsDataset(BaseDataset):
                 shape = (m, 3, size, size)
             else:                             # whole images of the network's input size
                 shape = (m, 3, opt.img_height, opt.img_width)
-            self.pool_A = torch.rand(*shape, device=self.device, generator=g)
-            self.pool_B = torch.rand(*shape, device=self.device, generator=g)
+            if getattr(opt, 'synthetic_pairs', 'independent') == 'mapped':
+                self.pool_A = self._texture(shape, g)
+                self.pool_B = self._remap(self.pool_A)
+            else:
+                self.pool_A = torch.rand(*shape, device=self.device, generator=g)
+                self.pool_B = torch.rand(*shape, device=self.device, generator=g)
             self.paths_A = ['synthetic/A/%05d' % i for i in range(m)]
             self.paths_B = ['synthetic/B/%05d' % i for i in range(m)]
         else:
@@ -64,6 +93,42 @@ class GpuPairsDataset(BaseDataset):
         # what a batch looks like: a square crop, or the whole image
         self.out_hw = (opt.crop_size, opt.crop_size) if 'crop' in self.pre else (self.H, self.W)
         assert self.H >= self.out_hw[0] and self.W >= self.out_hw[1], "images smaller than the crop"
+
+    def _texture(self, shape, g):
+        """band-limited random texture in [0, 1]: two octaves of seeded coarse noise (1/16 and 1/4 of the side), each upsampled once with the
+        bicubic filter _resize uses, stretched to the full range per image — structure at the scales a registration network can lock on to"""
+        m, c, h, w = shape
+        out = None
+        for div, weight in ((16, 0.65), (4, 0.35)):
+            coarse = torch.rand(m, c, max(2, h // div), max(2, w // div), device=self.device, generator=g)
+            up = torch.nn.functional.interpolate(coarse, size=(h, w), mode='bicubic', align_corners=False) * weight
+            out = up if out is None else out + up
+        lo, hi = out.amin(dim=(1, 2, 3), keepdim=True), out.amax(dim=(1, 2, 3), keepdim=True)
+        return ((out - lo) / (hi - lo).clamp_min(1e-6)).clamp_(0.0, 1.0).contiguous()
+
+    @staticmethod
+    def _remap(a):
+        """the second modality of a `mapped` synthetic pair: a fixed, per-channel, non-linear (one of them decreasing) map of the first"""
+        maps = (lambda v: 1.0 - v * v, lambda v: 0.5 - 0.5 * torch.cos(math.pi * v), lambda v: v.sqrt())
+        return torch.stack([maps[ch % 3](a[:, ch]) for ch in range(a.shape[1])], dim=1).clamp_(0.0, 1.0).contiguous()
+
+    def _draw_misalign(self, n):
+        """[n, 6 + 2 L L] float32 parameter rows of nemar_deform_field: a11 a12 tx a21 a22 ty (scale * rotation about the crop centre +
+        translation; the identity without `affine`), then the [2, L, L] lattice (L = 0 without `elastic`)"""
+        opt, rng, L = self.opt, self.rng_misalign, self.lattice
+        max_px = float(getattr(opt, 'misalign_max_px', 8.0))
+        rows = np.zeros((n, 6 + 2 * L * L), dtype=np.float32)
+        for b in range(n):
+            a11, a12, tx, a21, a22, ty = 1.0, 0.0, 0.0, 0.0, 1.0, 0.0
+            if self.misalign in ('affine', 'both'):
+                th = math.radians(rng.uniform(-1.0, 1.0) * float(getattr(opt, 'misalign_rot_deg', 5.0)))
+                sc = 1.0 + rng.uniform(-1.0, 1.0) * float(getattr(opt, 'misalign_scale', 0.05))
+                a11, a12, a21, a22 = sc * math.cos(th), -sc * math.sin(th), sc * math.sin(th), sc * math.cos(th)
+                tx, ty = rng.uniform(-max_px, max_px), rng.uniform(-max_px, max_px)
+            rows[b, :6] = (a11, a12, tx, a21, a22, ty)
+            for k in range(2 * L * L):
+                rows[b, 6 + k] = rng.uniform(-max_px, max_px)
+        return rows
 
     def _resize(self, pool):
         """the image-only part of get_transform: resize / scale_width / make_power_2 (reference data/base_dataset.py:86-99), once"""
@@ -102,17 +167,27 @@ class GpuPairsDataset(BaseDataset):
             params[b] = (i % self.M, y0, x0, int(p['flip']))
         d_params = torch.from_numpy(params).to(self.device, non_blocking=True)
         out = {}
+        gt = None
+        if self.misalign != 'none':
+            self._last_misalign = self._draw_misalign(len(indices))
+            d_mis = torch.from_numpy(self._last_misalign).to(self.device, non_blocking=True)
+            gt = ops.deform_field(d_mis, len(indices), hc, wc, self.lattice, self.lattice)
         st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
         for key, pool in (('A', self.pool_A), ('B', self.pool_B)):
+            if key == 'A' and gt is not None:
+                out[key] = ops.crop_flip_deform_normalize(pool, d_params, gt, hc, wc, 1.0)
+                continue
             y = torch.empty((len(indices), 3, hc, wc), dtype=torch.float32, device=self.device)
             ops.L.crop_flip_normalize(ctypes.c_void_p(pool.data_ptr()), ctypes.c_void_p(d_params.data_ptr()),
                                       ctypes.c_void_p(y.data_ptr()), self.M, len(indices), 3, self.H, self.W, hc, wc, 1.0, st)
             out[key] = y
         out['A_paths'] = [self.paths_A[i % self.M] for i in indices]
         out['B_paths'] = [self.paths_B[i % self.M] for i in indices]
+        if gt is not None:
+            out['gt_field'] = gt
         self._last_params = params
         return out
 
     def __getitem__(self, index):
         b = self.batch([index])
-        return {'A': b['A'][0], 'B': b['B'][0], 'A_paths': b['A_paths'][0], 'B_paths': b['B_paths'][0]}
+        return {k: v[0] for k, v in b.items()}

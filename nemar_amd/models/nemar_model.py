@@ -91,6 +91,8 @@ class NEMARModel(BaseModel):
             parser.add_argument('--tbvis_iteration_update_rate', type=int, default=1000)
             parser.add_argument('--tbvis_disable_report_weights', action='store_true')
             parser.add_argument('--tbvis_disable_report_offsets', action='store_true')
+            # (MI355X build) the registration-error scalars of batches that carry a ground-truth field (--misalign): on unless disabled
+            parser.add_argument('--tbvis_disable_report_registration', action='store_true')
         return parser
 
     def __init__(self, opt):
@@ -178,7 +180,27 @@ class NEMARModel(BaseModel):
         self.real_A = input[a].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
         self.real_B = input[b].to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
         self.image_paths = input[a + '_paths']
+        # known-misalignment pairs (data/gpupairs_dataset.py --misalign): the field that deformed modality A, [N,2,H,W] in pixels
+        gt = input.get('gt_field')
+        if gt is not None and not AtoB:
+            raise ValueError('gt_field describes the deformation of modality A: the registration error is defined for --direction AtoB')
+        self.gt_field = None if gt is None else gt.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
         self._resized = {}
+
+    def registration_error(self):
+        """How far the last forward pass (a training step or test()) is from undoing the batch's known misalignment: a dict of Python
+        floats — epe_px (mean |S(x) + g(S(x)) - x| over the pixels whose sampling position S(x) is inside the image), epe_before_px
+        (mean |g|: the error of doing nothing), max_px, fold_frac, valid_frac.  One host synchronisation."""
+        from ..util.visualizer import registration_summary
+        if getattr(self, 'gt_field', None) is None:
+            raise RuntimeError('registration_error: the current batch carries no gt_field (train with --misalign affine|elastic|both)')
+        pred = self.netR.last_prediction()
+        if pred is None:
+            raise RuntimeError('registration_error: no forward pass yet')
+        rows = ops.registration_error(pred[0], self.gt_field, pred[1])
+        cols = rows.sum(0)
+        cols[2] = rows[:, 2].max()
+        return registration_summary(cols.tolist(), self.gt_field.size(0) * self.gt_field.size(2) * self.gt_field.size(3))
 
     # ---- forward -------------------------------------------------------------------------------------------
     def forward(self):

@@ -72,7 +72,14 @@ class AffineSTN(nn.Module):
 
     # predict -> warp* -> regularization: same split as UnetSTN (see there)
     def predict(self, img_a, img_b):
-        return self.net(img_a, img_b)
+        dtheta = self.net(img_a, img_b)
+        self.last_dtheta = dtheta.detach()         # for the registration-error meter (util/visualizer.RegistrationMeter); no copy
+        return dtheta
+
+    def last_prediction(self):
+        """(what the last forward pass handed to the warp kernel, its grid mode) — None before the first pass"""
+        d = getattr(self, 'last_dtheta', None)
+        return None if d is None else (d, ops.GRID_AFFINE)
 
     def warp(self, field, imgs):
         return ops.warp_affine(field, list(imgs))

@@ -114,6 +114,11 @@ class UnetSTN(nn.Module):
         self.last_offsets = d_up.detach()          # for the offset statistics (util/visualizer.OffsetMeter); no copy
         return d, d_up
 
+    def last_prediction(self):
+        """(what the last forward pass handed to the warp kernel, its grid mode) — None before the first pass"""
+        d = getattr(self, 'last_offsets', None)
+        return None if d is None else (d, ops.GRID_UNET)
+
     def get_grid(self, img_a, img_b, return_offsets_only=False):
         """The sampling grid [N,H,W,2] aligning img_a with img_b (reference :131-146).  Built with torch ops: this is
         the inspection API, not the training path (the kernels never materialise the grid)."""

@@ -1682,6 +1682,49 @@ def grid_sample(img, grid):
     return _Warp.apply(grid, GRID_EXPLICIT, int(grid.shape[1]), int(grid.shape[2]), img)[0]
 
 
+# ---- known misalignment: ground-truth fields, the deforming input pipeline, the registration-error meter (no autograd: data and read-outs) ----
+def deform_field(params, B, Hc, Wc, gh, gw):
+    """params [B, 6 + 2*gh*gw] (a11 a12 tx a21 a22 ty about the crop centre, then a [2,gh,gw] lattice of pixel displacements; gh = gw = 0:
+    none) -> the ground-truth field g [B,2,Hc,Wc] in pixels, channel 0 = x."""
+    params = _c(params.detach())
+    if tuple(params.shape) != (B, 6 + 2 * gh * gw):
+        raise ValueError("deform_field: params %s, expected (%d, %d)" % (tuple(params.shape), B, 6 + 2 * gh * gw))
+    g = torch.empty((B, 2, Hc, Wc), dtype=torch.float32, device=params.device)
+    L.deform_field(_p(params), _p(g), B, Hc, Wc, gh, gw, _stream())
+    return g
+
+
+def crop_flip_deform_normalize(pool, crop_params, g, Hc, Wc, scale=1.0):
+    """crop_flip_normalize of pool [M,C,H,W] by crop_params [B,4] int32 (pool index, y0, x0, flip), each output pixel q read bilinearly
+    at q + g(q) (g [B,2,Hc,Wc] in pixels), border-clamped to the crop window -> [B,C,Hc,Wc] in [-1, 1]."""
+    pool, g = _c(pool), _c(g.detach())
+    M, C, H, W = pool.shape
+    B = crop_params.shape[0]
+    if crop_params.dtype != torch.int32 or tuple(crop_params.shape) != (B, 4) or tuple(g.shape) != (B, 2, Hc, Wc):
+        raise ValueError("crop_flip_deform_normalize: crop_params [B,4] int32 and g [B,2,Hc,Wc] expected")
+    y = torch.empty((B, C, Hc, Wc), dtype=torch.float32, device=pool.device)
+    L.crop_flip_deform_normalize(_p(pool), _p(crop_params.contiguous()), _p(g), _p(y), M, B, C, H, W, Hc, Wc, float(scale), _stream())
+    return y
+
+
+REG_COLUMNS = ('valid_count', 'sum_r', 'max_r', 'sum_g', 'fold_count', 'interior_count')
+
+
+def registration_error(pred, g, mode):
+    """The registration-error meter: pred = the STN's prediction (mode GRID_UNET: offsets [N,2,H,W]; GRID_AFFINE: dtheta [N,6]) against the
+    ground-truth field g [N,2,H,W] -> device tensor [N,6], columns REG_COLUMNS (sums and counts: the caller divides).  No sync."""
+    pred, g = _c(pred.detach()), _c(g.detach())
+    N, _, H, W = g.shape
+    want = (N, 2, H, W) if mode == GRID_UNET else (N, 6)
+    if tuple(pred.shape) != want:
+        raise ValueError("registration_error: prediction %s, expected %s for a field %s" % (tuple(pred.shape), want, tuple(g.shape)))
+    out = torch.empty((N, 6), dtype=torch.float32, device=g.device)
+    wsb = Q.registration_error_workspace(N, H, W)
+    ws = _workspace(wsb, g.device)
+    L.registration_error(_p(pred), mode, _p(g), _p(out), _p(ws), wsb, N, H, W, _stream())
+    return out
+
+
 class _Smoothness(Function):
     @staticmethod
     def forward(ctx, d, img, alpha, factor):

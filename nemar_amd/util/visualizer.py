@@ -96,6 +96,42 @@ class OffsetMeter:
         return mx, my
 
 
+def registration_summary(cols, pixels):
+    """the six column totals of ops.registration_error (ops.REG_COLUMNS; the maximum column max-ed) over `pixels` pixels -> the five
+    reported numbers.  A batch without a single valid pixel has no error to average: epe_px and max_px are 0 and valid_frac says why."""
+    valid, sum_r, max_r, sum_g, fold, interior = cols
+    return {'epe_px': sum_r / valid if valid > 0 else 0.0, 'epe_before_px': sum_g / pixels if pixels > 0 else 0.0, 'max_px': max_r,
+            'fold_frac': fold / interior if interior > 0 else 0.0, 'valid_frac': valid / pixels if pixels > 0 else 0.0}
+
+
+class RegistrationMeter:
+    """Registration error against the batch's ground-truth field (--misalign), accumulated ON THE DEVICE: update() runs the meter kernel
+    on the step's own prediction and folds its [N,6] rows into a device accumulator (sums added, the maximum max-ed; no sync); read()
+    transfers seven floats, returns the summary of everything since the last read (None if nothing was added) and resets."""
+
+    def __init__(self, device):
+        self.acc = torch.zeros(6, dtype=torch.float32, device=device)
+        self.max = torch.zeros(1, dtype=torch.float32, device=device)
+        self.pixels = 0
+
+    def update(self, pred, mode, gt_field):
+        rows = ops.registration_error(pred, gt_field, mode)
+        self.acc.add_(rows.sum(0))
+        self.max = torch.maximum(self.max, rows[:, 2].max().reshape(1))
+        self.pixels += gt_field.size(0) * gt_field.size(2) * gt_field.size(3)
+
+    def read(self):
+        if self.pixels == 0:
+            return None
+        cols = torch.cat([self.acc, self.max]).tolist()          # the only device->host transfer
+        cols[2] = cols.pop()
+        out = registration_summary(cols, self.pixels)
+        self.acc.zero_()
+        self.max.zero_()
+        self.pixels = 0
+        return out
+
+
 class TrainingMonitor:
     """What train.py drives every iteration (reference TensorboardVisualizer.iteration_step, tb_visualizer.py:68-85)."""
 
@@ -105,7 +141,9 @@ class TrainingMonitor:
         self.report_offsets = not getattr(opt, 'tbvis_disable_report_offsets', False)
         self.report_weights = not getattr(opt, 'tbvis_disable_report_weights', False)
         self.log = ScalarLog(opt)
+        self.report_registration = not getattr(opt, 'tbvis_disable_report_registration', False)
         self.meter = OffsetMeter(model.device)
+        self.reg_meter = RegistrationMeter(model.device)
         self.iteration_cnt = 0
         self.save_count = 0
 
@@ -113,6 +151,11 @@ class TrainingMonitor:
         field = getattr(self.model, 'deformation_field_A_to_B', None)
         if self.report_offsets and field is not None and field.dim() == 4 and field.size(1) == 2:
             self.meter.update(field)
+        gt = getattr(self.model, 'gt_field', None)
+        if self.report_registration and gt is not None:
+            pred = self.model.netR.last_prediction()             # the prediction of the step's own forward pass: R is not run again
+            if pred is not None:
+                self.reg_meter.update(pred[0], pred[1], gt)
         if self.rate <= 0:
             return
         if self.iteration_cnt == 0:
@@ -124,6 +167,7 @@ class TrainingMonitor:
                 mx, my = self.meter.means()
                 self.log.add_scalar('offset/mean_x', mx, self.save_count)
                 self.log.add_scalar('offset/mean_y', my, self.save_count)
+            self.write_registration()
             self.save_count += 1
         self.iteration_cnt = (self.iteration_cnt + 1) % self.rate
 
@@ -149,7 +193,14 @@ class TrainingMonitor:
             mx, my = self.meter.means()
             self.log.add_scalar('offset/mean_x', mx, self.save_count)
             self.log.add_scalar('offset/mean_y', my, self.save_count)
+        self.write_registration()
         self.save_count += 1
+
+    def write_registration(self):
+        """'registration/<name>' of everything metered since the last report (nothing without a ground-truth field)"""
+        summary = self.reg_meter.read() if self.report_registration else None
+        for name, v in (summary or {}).items():
+            self.log.add_scalar('registration/{}'.format(name), v, self.save_count)
 
     def end(self):
         if self.log.writer is not None:
