@@ -3,10 +3,10 @@
 //
 // Replaces nn.BatchNorm2d at reference models/networks.py:22 (norm_layer of ResnetGenerator :351,358,373, ResnetBlock :426,439,
 // UnetSkipConnectionBlock :517,519, NLayerDiscriminator :584,592, PixelDiscriminator :626) with `--norm batch`.
-//   train fwd:  mean, var = biased statistics over (N, H, W) of a SEGMENT of the batch;  scale = gamma * rstd, shift = beta - mean * scale
-//               y = [residual +] dropout(act(x * scale + shift));  running = (1 - momentum) running + momentum (mean | unbiased var)
+//   train fwd:  mean, var = biased statistics over (N, H, W) of a SEGMENT of the batch;  scale = gamma * rstd
+//               y = [residual +] dropout(act((x - mean) * scale + beta));  running = (1 - momentum) running + momentum (mean | unbiased var)
 //   eval fwd:   the same with the running statistics (left untouched)
-//   bwd:        z = x * scale + shift (recomputed), g = gy [* mask / (1 - p)] * act'(z), xhat = (x - mean) * rstd
+//   bwd:        z = (x - mean) * scale + beta (recomputed; NOT x * scale + (beta - mean * scale): three roundings the size of mean * scale), g = gy [* mask / (1 - p)] * act'(z), xhat = (x - mean) * rstd
 //               dgamma += sum g xhat, dbeta += sum g;  gx = gamma rstd (g - sum g / M - xhat sum(g xhat) / M)   (eval: gx = gamma rstd g)
 //
 // Segments: the N samples form S equal segments (the model's batched passes: T over [a ; R(a)], D over [real ; fakes]); statistics,
@@ -176,19 +176,22 @@ __global__ __launch_bounds__(256) void bn_fwd_partials_kernel(const float* __res
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-    const float mean = wave_sum(s) / (float)len;
-    float q = 0.f;
+    const float m0 = wave_sum(s) / (float)len;
+    float q = 0.f, e = 0.f;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float d = k * 256 + lane * 4 + j < len ? v[k][j] - mean : 0.f;
+            const float d = k * 256 + lane * 4 + j < len ? v[k][j] - m0 : 0.f;
+            e += d;
             q += d * d;
         }
     }
-    q = wave_sum(q);
+    // (the sum of the deviations takes the rounding of m0 — an ulp of a mean far from zero — out of the mean and of M2)
+    const float c = wave_sum(e) / (float)len;
+    q = fmaxf(wave_sum(q) - (float)len * (c * c), 0.f);
     if (lane == 0) {
-        part[2 * piece] = mean;
+        part[2 * piece] = m0 + c;
         part[2 * piece + 1] = q;
     }
 }
@@ -209,7 +212,15 @@ __global__ __launch_bounds__(256) void bn_fwd_merge_kernel(const float* __restri
             const long long piece = ((long long)n * sh.C + c) * sh.P + p;
             a += (float)piece_len(sh, p) * part[2 * piece];
         }
-        const float mean = block_sum(a, red) / M;
+        const float m0 = block_sum(a, red) / M;
+        // (... and once more as deviations from m0: what is left of the error is an ulp of the pieces' spread, not of their size)
+        float e = 0.f;
+        for (int i = threadIdx.x; i < items; i += 256) {
+            const int n = s * Ns + i / sh.P, p = i % sh.P;
+            const long long piece = ((long long)n * sh.C + c) * sh.P + p;
+            e += (float)piece_len(sh, p) * (part[2 * piece] - m0);
+        }
+        const float mean = m0 + block_sum(e, red) / M;
         float b = 0.f;
         for (int i = threadIdx.x; i < items; i += 256) {
             const int n = s * Ns + i / sh.P, p = i % sh.P;
@@ -250,7 +261,7 @@ __device__ __forceinline__ unsigned bn_finite_mag(float v) {
     return u < 0x7f800000u ? u : 0u;
 }
 
-// ---- forward launch 3 (training and eval): y = [residual +] dropout(act(x * scale + shift)) -------------------------------------
+// ---- forward launch 3 (training and eval): y = [residual +] dropout(act((x - mean) * scale + beta)) -------------------------------------
 // grid (ceil(C * P / 4), N): the four waves of a workgroup take four consecutive pieces of sample blockIdx.y
 template <bool VEC>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ residual, float* __restrict__ y,
@@ -269,7 +280,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         float mean, rstd;
         bn_stats(mean_src, var_src, from_var, eps, sh.S, sh.C, s, c, mean, rstd);
         const float scale = gamma[c] * rstd;
-        const float shift = beta[c] - mean * scale;
+        const float shift = beta[c];
         if (saved_out && n == 0 && p == 0 && lane == 0) {      // (eval: the statistics the backward pass uses)
             saved_out[c] = mean;
             saved_out[sh.C + c] = rstd;
@@ -281,7 +292,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) v[k][j] = bn_act(v[k][j] * scale + shift, act, slope);
+            for (int j = 0; j < 4; ++j) v[k][j] = bn_act((v[k][j] - mean) * scale + shift, act, slope);
         if (drop.on) {
             float m[4][4];
             bn_masks<VEC>(drop, gbase, len, lane, m);
@@ -311,7 +322,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     if (maxw) bn_publish_max(omax, maxw, red);
 }
 
-// g = gy [* mask / (1 - p)] * act'(x * scale + shift) and xhat of the lane's 16 elements (zeros past the piece's end)
+// g = gy [* mask / (1 - p)] * act'((x - mean) * scale + beta) and xhat of the lane's 16 elements (zeros past the piece's end)
 template <bool VEC>
 __device__ __forceinline__ void bn_bwd_load(const float* __restrict__ x, const float* __restrict__ gy, long long gbase, int len, int lane,
                                             float mean, float rstd, float scale, float shift, int act, float slope, const BnDrop& drop,
@@ -328,7 +339,7 @@ __device__ __forceinline__ void bn_bwd_load(const float* __restrict__ x, const f
             const float xv = xh[k][j];
             float t = g[k][j];
             if (drop.on) t = m[k][j] != 0.f ? t * drop.scale : 0.f;
-            t = t * bn_act_d(xv * scale + shift, act, slope);
+            t = t * bn_act_d((xv - mean) * scale + shift, act, slope);
             g[k][j] = on ? t : 0.f;
             xh[k][j] = on ? (xv - mean) * rstd : 0.f;
         }
@@ -352,7 +363,7 @@ __global__ __launch_bounds__(256) void bn_bwd_partials_kernel(const float* __res
     float mean, rstd;
     bn_stats(stats, nullptr, 0, 0.f, sh.S, sh.C, s, c, mean, rstd);
     const float scale = gamma[c] * rstd;
-    const float shift = beta[c] - mean * scale;
+    const float shift = beta[c];
     const int len = piece_len(sh, p);
     float g[4][4], xh[4][4];
     bn_bwd_load<VEC>(x, gy, plane * sh.HW + (long long)p * PIECE, len, lane, mean, rstd, scale, shift, act, slope, drop, g, xh);
@@ -418,7 +429,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     float mean, rstd;
     bn_stats(stats, nullptr, 0, 0.f, sh.S, sh.C, s, c, mean, rstd);
     const float scale = gamma[c] * rstd;
-    const float shift = beta[c] - mean * scale;
+    const float shift = beta[c];
     const float M = (float)(sh.N / sh.S) * (float)sh.HW;
     const float m1 = training ? sums[2 * (s * sh.C + c)] / M : 0.f;
     const float m2 = training ? sums[2 * (s * sh.C + c) + 1] / M : 0.f;

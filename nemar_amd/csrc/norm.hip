@@ -53,13 +53,41 @@ __device__ __forceinline__ void publish_max(unsigned m, unsigned* maxw, int pps,
     }
 }
 
-// PER > 0: register-cached plane (HW <= THREADS*PER).  PER == 0: streaming (shifted one-pass statistics).
+// Sums of two values at once (one barrier pair): `red` is >= 32 floats of LDS.  Fixed tree, as block_sum.
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    a = wave_sum(a);
+    b = wave_sum(b);
+    __syncthreads();
+    if (lane == 0) { red[wid] = a; red[16 + wid] = b; }
+    __syncthreads();
+    float ta = 0.f, tb = 0.f;
+    for (int i = 0; i < nw; ++i) { ta += red[i]; tb += red[16 + i]; }
+    a = ta;
+    b = tb;
+}
+
+// The statistics of every forward kernel here: m0 = sum / HW, then the deviations d = x - m0 — their squares for the variance and their sum
+// e, which takes the rounding of m0 (an ulp of a mean far from zero: 6e-5 at 1000) out of both:  mean = m0 + e / HW,
+// var = sum d^2 / HW - (e / HW)^2.  The register-cached kernels apply the correction c = e / HW only where it is worth more than
+// 2^-17 of a standard deviation in xhat (a quarter of the 3e-5 the output is held to): below that it is beneath the rounding of the
+// output itself, and mean and rstd stay the plain two-pass values.  The streaming kernel always applies it.
+constexpr float MEAN_CORR_MIN = 7.62939453125e-6f;        // 2^-17
+__device__ __forceinline__ void corrected_stats(float m0, float c, float var0, float eps, float& mean, float& rstd) {
+    mean = m0;
+    rstd = 1.f / sqrtf(var0 + eps);
+    if (fabsf(c) * rstd > MEAN_CORR_MIN) {
+        mean = m0 + c;
+        rstd = 1.f / sqrtf(fmaxf(var0 - c * c, 0.f) + eps);
+    }
+}
+// PER > 0: register-cached plane (HW <= THREADS*PER).  PER == 0: streaming (two statistics passes, then the output pass).
 template <int THREADS, int PER>
 __global__ __launch_bounds__(THREADS) void instnorm_fwd_kernel(const float* __restrict__ x,
                                                                const float* __restrict__ residual,
                                                                float* __restrict__ y, float* __restrict__ stats, int HW,
                                                                float eps, int act, float slope, unsigned* maxw, int pps) {
-    __shared__ float red[16];
+    __shared__ float red[32];
     unsigned omax = 0;                                    // max |y| of this plane (maxw != null)
     const size_t base = (size_t)blockIdx.x * HW;
     const float* xp = x + base;
@@ -76,15 +104,17 @@ __global__ __launch_bounds__(THREADS) void instnorm_fwd_kernel(const float* __re
             v[k] = i < HW ? xp[i] : 0.f;
             s += v[k];
         }
-        mean = block_sum(s, red) * inv;
-        float q = 0.f;
+        const float m0 = block_sum(s, red) * inv;
+        float q = 0.f, e = 0.f;
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int i = threadIdx.x + k * THREADS;
-            const float d = i < HW ? v[k] - mean : 0.f;
+            const float d = i < HW ? v[k] - m0 : 0.f;
+            e += d;
             q += d * d;
         }
-        rstd = 1.f / sqrtf(block_sum(q, red) * inv + eps);
+        block_sum2(e, q, red);
+        corrected_stats(m0, e * inv, q * inv, eps, mean, rstd);
 #pragma unroll
         for (int k = 0; k < PER; ++k) {
             const int i = threadIdx.x + k * THREADS;
@@ -96,17 +126,22 @@ __global__ __launch_bounds__(THREADS) void instnorm_fwd_kernel(const float* __re
             }
         }
     } else {
-        const float shift = xp[0];
-        float s = 0.f, q = 0.f;
+        // two passes for the statistics, the second from the memory-side cache: the mean, then the deviations from THAT mean — their squares
+        // for the variance, their sum to take the first pass's rounding out of both (no element of the plane is special: a shift taken
+        // from xp[0] cancelled in E[d^2] - E[d]^2 as soon as the first pixel sat far from the plane's mean)
+        float s = 0.f;
+        for (int i = threadIdx.x; i < HW; i += THREADS) s += xp[i];
+        const float m0 = block_sum(s, red) * inv;
+        float e = 0.f, q = 0.f;
         for (int i = threadIdx.x; i < HW; i += THREADS) {
-            const float d = xp[i] - shift;
-            s += d;
+            const float d = xp[i] - m0;
+            e += d;
             q += d * d;
         }
-        const float ms = block_sum(s, red) * inv;
-        const float var = fmaxf(block_sum(q, red) * inv - ms * ms, 0.f);
-        mean = shift + ms;
-        rstd = 1.f / sqrtf(var + eps);
+        block_sum2(e, q, red);
+        const float c = e * inv;
+        mean = m0 + c;
+        rstd = 1.f / sqrtf(fmaxf(q * inv - c * c, 0.f) + eps);
         for (int i = threadIdx.x; i < HW; i += THREADS) {
             float o = act_f((xp[i] - mean) * rstd, act, slope);
             if (rp) o += rp[i];
@@ -131,7 +166,7 @@ template <int THREADS, int PER4, bool FULL>
 __global__ __launch_bounds__(THREADS) void instnorm_fwd4_kernel(const float* __restrict__ x, const float* __restrict__ residual,
                                                                 float* __restrict__ y, float* __restrict__ stats, int HW, float eps, int act,
                                                                 float slope, unsigned* maxw, int pps) {
-    __shared__ float red[16];
+    __shared__ float red[32];
     unsigned omax = 0;
     const size_t base = (size_t)blockIdx.x * HW;
     const f32x4n* xp = reinterpret_cast<const f32x4n*>(x + base);
@@ -151,16 +186,19 @@ __global__ __launch_bounds__(THREADS) void instnorm_fwd4_kernel(const float* __r
         if (!FULL && threadIdx.x + k * THREADS >= n4) v[k] = f32x4n{0.f, 0.f, 0.f, 0.f};
         s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
     }
-    const float mean = uniform_f(block_sum(s, red) * inv);        // (wave-uniform values live in scalar registers)
-    float q = 0.f;
+    const float m0 = uniform_f(block_sum(s, red) * inv);          // (wave-uniform values live in scalar registers)
+    float q = 0.f, ds = 0.f;
 #pragma unroll
     for (int k = 0; k < PER4; ++k) {
         if (FULL || threadIdx.x + k * THREADS < n4) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { const float d = v[k][e] - mean; q += d * d; }
+            for (int e = 0; e < 4; ++e) { const float d = v[k][e] - m0; ds += d; q += d * d; }
         }
     }
-    const float rstd = uniform_f(1.f / sqrtf(block_sum(q, red) * inv + eps));
+    block_sum2(ds, q, red);
+    float mean_v, rstd_v;
+    corrected_stats(m0, ds * inv, q * inv, eps, mean_v, rstd_v);
+    const float mean = uniform_f(mean_v), rstd = uniform_f(rstd_v);
     // (the residual is fetched in groups of four float4 per thread: all PER4 at once would double the register footprint)
     constexpr int RG = PER4 >= 16 ? 1 : (PER4 < 4 ? PER4 : (PER4 % 4 == 0 ? 4 : (PER4 % 2 == 0 ? 2 : 1)));
     static_assert(PER4 % RG == 0, "residual groups must tile the float4s of a thread");

@@ -165,8 +165,23 @@ __global__ __launch_bounds__(1024) void instnorm_planes_kernel(NormPlanesParams 
         s[j] = q;
     }
     if (!(p.dbg & 4)) block_sum8(s, red, tot); else { for (int j = 0; j < 8; ++j) tot[j] = s[j] * 1024.f; }
+    // (the sum of the deviations takes the rounding of the first mean — an ulp of a mean far from zero — out of mean, variance and xhat,
+    // where it is worth more than 2^-17 of a standard deviation, as in norm.hip; below that the plain two-pass values stand)
+    float corr[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) rstd[j] = 1.f / sqrtf(tot[j] * inv + p.eps);
+    for (int j = 0; j < 8; ++j) s[j] = (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
+    if (!(p.dbg & 4)) block_sum8(s, red, corr); else { for (int j = 0; j < 8; ++j) corr[j] = s[j] * 1024.f; }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const float c = corr[j] * inv;
+        rstd[j] = 1.f / sqrtf(tot[j] * inv + p.eps);
+        if (fabsf(c) * rstd[j] > 7.62939453125e-6f) {            // 2^-17 (uniform over the workgroup)
+            mean[j] += c;
+            rstd[j] = 1.f / sqrtf(fmaxf(tot[j] * inv - c * c, 0.f) + p.eps);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[j][e] = active ? v[j][e] - c : 0.f;
+        }
+    }
 #pragma unroll
     for (int j = 0; j < 8; ++j)
         if (t == j) {

@@ -86,21 +86,52 @@ def ref_backward(x, gy, gamma, mean, rstd, S, act_mask, training=True):
 
 
 def _z32(x, gamma, beta, mean, rstd, S):
-    """z = x * scale + shift in float32 with the kernel's operation order (scale = gamma * rstd, shift = beta - mean * scale)"""
+    """z = (x - mean) * scale + beta in float32 with the kernel's operation order (scale = gamma * rstd)"""
     f = np.float32
     N = x.shape[0]
     Ns = N // S
     z = np.empty_like(x, dtype=f)
     for s in range(S):
         sc = (gamma.astype(f) * rstd[s].astype(f)).astype(f)
-        sh = (beta.astype(f) - (mean[s].astype(f) * sc).astype(f)).astype(f)
-        z[s * Ns:(s + 1) * Ns] = (x[s * Ns:(s + 1) * Ns] * sc[None, :, None, None]).astype(f) + sh[None, :, None, None]
+        d = (x[s * Ns:(s + 1) * Ns] - mean[s].astype(f)[None, :, None, None]).astype(f)
+        z[s * Ns:(s + 1) * Ns] = (d * sc[None, :, None, None]).astype(f) + beta.astype(f)[None, :, None, None]
     return z
 
 
-def _inputs(N, C, H, W, seed):
+BN_FAMILIES = ("plain", "offset", "first_outlier", "first_outlier_far", "last_outlier", "spike", "constant", "tiny", "mixed")
+
+
+def _family_x(rng, N, C, H, W, family):
+    """the plane families of tests/norm_cases.py with the statistics per channel over (N, H, W)"""
+    if family == "plain":
+        return rng.standard_normal((N, C, H, W)) * 1.5 + rng.standard_normal((1, C, 1, 1)) * 2
+    if family == "constant":                                # uneven over the samples: sample 0 is 0, every other sample 1 — the merge of
+        return np.broadcast_to((np.arange(N) > 0).astype(np.float64).reshape(N, 1, 1, 1), (N, C, H, W)).copy()   # per-piece (mean, M2) pairs
+    if family == "spike":
+        x = np.zeros((N, C, H, W))
+        x[N - 1, np.arange(C), (np.arange(C) * 3 + H // 3) % H, (np.arange(C) * 5 + W // 2) % W] = 5.0
+        return x
+    x = rng.standard_normal((N, C, H, W))
+    if family == "offset":                                  # a different offset per channel
+        x += (1000.0 / (1 + np.arange(C)) * (-1.0) ** np.arange(C)).reshape(1, C, 1, 1)
+    elif family == "first_outlier":                         # element 0 of sample 0
+        x[0, :, 0, 0] = 30.0
+    elif family == "first_outlier_far":
+        x[0, :, 0, 0] = 1000.0
+    elif family == "last_outlier":
+        x[-1, :, -1, -1] = -30.0
+    elif family == "tiny":
+        x = 1e-4 * x + 1e-2
+    elif family == "mixed":
+        x *= (10.0 ** (((np.arange(C) * 5) % 7) - 3.0)).reshape(1, C, 1, 1)
+    else:
+        raise ValueError(family)
+    return x
+
+
+def _inputs(N, C, H, W, seed, family="plain"):
     rng = np.random.default_rng(seed)
-    x = (rng.standard_normal((N, C, H, W)) * 1.5 + rng.standard_normal((1, C, 1, 1)) * 2).astype(np.float32)
+    x = _family_x(rng, N, C, H, W, family).astype(np.float32)
     gamma = (1.0 + 0.3 * rng.standard_normal(C)).astype(np.float32)
     gamma[0] = -abs(gamma[0])                       # a negative scale: the sign of xhat is not the sign of z
     beta = (0.2 * rng.standard_normal(C)).astype(np.float32)
@@ -267,3 +298,93 @@ def case_batchnorm_single_value(be):
         with pytest.raises(NemarHipError, match="more than 1 value"):
             run_train(be, be.dev(np.ones((N, C, 1, 1))), None, d_g, d_b, be.dev(np.zeros(C)), be.dev(np.ones(C)), _i64(be, 0), N, C, 1, S,
                       ACT_NONE)
+
+
+# ---- ill-conditioned channels (the families of tests/norm_cases.py) --------------------------------------------------------------------
+def _np32_bn(x, g, gamma, beta, rv, S):
+    """plain numpy fp32 exact two-pass BatchNorm2d (training) per segment -> y, mean[S,C], rstd[S,C], running_var, gx, dgamma, dbeta"""
+    f = np.float32
+    N, C = x.shape[:2]
+    Ns = N // S
+    y, gx = np.empty_like(x), np.empty_like(x)
+    rv = rv.astype(f).copy()
+    dg, db = np.zeros(C, dtype=f), np.zeros(C, dtype=f)
+    means, rstds = [], []
+    ga, be_ = gamma.astype(f).reshape(1, C, 1, 1), beta.astype(f).reshape(1, C, 1, 1)
+    for s in range(S):
+        sl = slice(s * Ns, (s + 1) * Ns)
+        xs, gs = x[sl], g[sl].astype(f)
+        M = f(xs.size // C)
+        m = (xs.sum(axis=(0, 2, 3), keepdims=True, dtype=f) / M).astype(f)
+        d = (xs - m).astype(f)
+        var = ((d * d).sum(axis=(0, 2, 3), keepdims=True, dtype=f) / M).astype(f)
+        rstd = (f(1) / np.sqrt(var + f(EPS), dtype=f)).astype(f)
+        xh = (d * rstd).astype(f)
+        y[sl] = xh * ga + be_
+        rv = (f(1 - MOM) * rv + f(MOM) * (var.reshape(C) * (M / (M - f(1))))).astype(f)
+        sg, sgx = gs.sum(axis=(0, 2, 3), keepdims=True, dtype=f), (gs * xh).sum(axis=(0, 2, 3), keepdims=True, dtype=f)
+        gx[sl] = ga * rstd * (gs - sg / M - xh * (sgx / M))
+        dg, db = dg + sgx.reshape(C), db + sg.reshape(C)
+        means.append(m.reshape(C))
+        rstds.append(rstd.reshape(C))
+    return y, np.array(means), np.array(rstds), rv, gx, dg, db
+
+
+def _torch32_bn(x, g, gamma, beta, rm, rv, S):
+    """torch's fp32 layer on the CPU, one F.batch_norm call per segment, the backward through autograd -> y, running_var, gx, dgamma, dbeta"""
+    import torch
+    N = x.shape[0]
+    Ns = N // S
+    w, b = torch.tensor(gamma, requires_grad=True), torch.tensor(beta, requires_grad=True)
+    trm, trv = torch.tensor(rm.copy()), torch.tensor(rv.copy())
+    ys, gxs = [], []
+    for s in range(S):
+        t = torch.tensor(x[s * Ns:(s + 1) * Ns], requires_grad=True)
+        y = torch.nn.functional.batch_norm(t, trm, trv, w, b, True, MOM, EPS)
+        y.backward(torch.tensor(np.ascontiguousarray(g[s * Ns:(s + 1) * Ns], dtype=np.float32)))
+        ys.append(y.detach().numpy())
+        gxs.append(t.grad.numpy())
+    return np.concatenate(ys), trv.numpy(), np.concatenate(gxs), w.grad.numpy(), b.grad.numpy()
+
+
+def case_batchnorm_conditioned(be, N, C, H, W, S, family, seed=5):
+    """case_batchnorm_train on one family of ill-conditioned channels: saved mean / rstd, output, running variance, gx, dgamma, dbeta.
+    `plain` keeps case_batchnorm_train's assertions; every other family passes a quantity within max(that tolerance, F x the larger
+    error against float64 of torch's fp32 F.batch_norm and of a numpy fp32 two-pass restatement) — norm_cases.check, per channel."""
+    import norm_cases as NC
+    act = ACT_NONE if family in NC.NO_ACT_BACKWARD else ACT_LRELU
+    x, gamma, beta, rm, rv, gy, _ = _inputs(N, C, H, W, seed, family)
+    HW, Ns = H * W, N // S
+    route = "batchnorm N=%d HW=%d S=%d" % (N, HW, S)
+    names = [family] * (S * C)
+
+    def ch(a):                                   # [N, C, H, W] -> one row per (segment, channel)
+        return np.asarray(a, dtype=np.float64).reshape(S, Ns, C, HW).transpose(0, 2, 1, 3).reshape(S * C, Ns * HW)
+
+    d_x, d_gy, d_g, d_b = be.dev(x), be.dev(gy), be.dev(gamma), be.dev(beta)
+    d_rm, d_rv, cnt = be.dev(rm.copy()), be.dev(rv.copy()), _i64(be, 0)
+    d_y, saved = run_train(be, d_x, None, d_g, d_b, d_rm, d_rv, cnt, N, C, HW, S, act)
+    g64, b64 = gamma.astype(np.float64), beta.astype(np.float64)
+    want, m, rstd, _, wrv = ref_forward(x, g64, b64, rm, rv, S, act)
+    pre64 = ref_forward(x, g64, b64, rm, rv, S, ACT_NONE)[0]
+    sv = be.np(saved)
+    assert np.all(np.isfinite(sv)) and np.all(np.isfinite(be.np(d_y)))
+    mask = _act_d(_z32(x, gamma, beta, sv[0], sv[1], S), act)
+    g = (gy * mask).astype(np.float32)
+    ny, nm, nr, nrv, ngx, ndg, ndb = _np32_bn(x, g, gamma, beta, rv, S)
+    ty, trv, tgx, tdg, tdb = _torch32_bn(x, g, gamma, beta, rm, rv, S)
+    ex_gx, ex_dg, ex_db = ref_backward(x, g, g64, m, rstd, S, np.ones_like(x, dtype=np.float64))     # the exact layer: the yardsticks' target
+    pm = lambda a: np.abs(a).reshape(a.shape[0], -1).max(axis=1)
+    NC.check(be, route, names, "mean", sv[0].reshape(-1), m.reshape(-1), 2e-5, 1e-5, np.abs(nm - m).reshape(-1))
+    NC.check(be, route, names, "rstd", sv[1].reshape(-1), rstd.reshape(-1), 0.0, 3e-5, np.abs(nr - rstd).reshape(-1))
+    NC.check(be, route, names, "y", ch(be.np(d_y).reshape(x.shape)), ch(want), 5e-5, 3e-5, np.maximum(pm(ch(ny) - ch(pre64)), pm(ch(ty) - ch(pre64))))
+    NC.check(be, route, [family] * C, "running_var", be.np(d_rv), wrv, 2e-6, 3e-5, np.maximum(np.abs(nrv - wrv), np.abs(trv - wrv)))
+    assert _i64_value(be, cnt) == S
+    gw, gb = be.zeros(C), be.zeros(C)
+    d_gx = run_bwd(be, d_x, d_gy, d_g, d_b, saved, gw, gb, N, C, HW, S, True, act)
+    wgx, wdg, wdb = ref_backward(x, gy, g64, sv[0], sv[1], S, mask)
+    atol = 3e-5 * (np.abs(wgx).max() if family == "plain" else pm(ch(wgx)))
+    NC.check(be, route, names, "gx", ch(be.np(d_gx).reshape(x.shape)), ch(wgx), atol, 1e-4, np.maximum(pm(ch(ngx) - ch(ex_gx)), pm(ch(tgx) - ch(ex_gx))))
+    scale = np.sqrt(x.size / C)
+    NC.check(be, route, [family] * C, "dgamma", be.np(gw), wdg, 2e-5 * scale, 1e-5, np.maximum(np.abs(ndg - ex_dg), np.abs(tdg - ex_dg)))
+    NC.check(be, route, [family] * C, "dbeta", be.np(gb), wdb, 2e-5 * scale, 1e-5, np.maximum(np.abs(ndb - ex_db), np.abs(tdb - ex_db)))

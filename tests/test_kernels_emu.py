@@ -333,6 +333,8 @@ def test_conv_transpose_fwd(be, R, op):
 @pytest.mark.parametrize("act", [K.O.ACT_NONE, K.O.ACT_RELU, K.O.ACT_LRELU])
 def test_instnorm(be, H, W, act):
     K.case_instnorm(be, 2, 3, H, W, act, residual=(act == K.O.ACT_NONE))
+    if (H, W) == (31, 31):
+        K.case_instnorm(be, 10, 13, H, W, act, residual=(act == K.O.ACT_NONE))         # 130 planes
 
 
 def test_instnorm_256x256_planes_gy_in_registers(be):

@@ -326,6 +326,8 @@ def test_conv_hot_shapes(be, C0, C1, Kc, R, stride, pad, pm, HW):
 @pytest.mark.parametrize("act", [K.O.ACT_NONE, K.O.ACT_RELU, K.O.ACT_LRELU])
 def test_instnorm(be, H, W, act):
     K.case_instnorm(be, 2, 3, H, W, act, residual=(act == K.O.ACT_NONE))
+    if (H, W) == (31, 31):
+        K.case_instnorm(be, 10, 13, H, W, act, residual=(act == K.O.ACT_NONE))         # 130 planes
 
 
 def test_pointwise(be):
