@@ -3,6 +3,7 @@
 restatements of nn.BatchNorm2d(affine=True, track_running_stats=True) written here."""
 import numpy as np
 
+from backends import both_poisons
 from kernel_cases import _assert_close
 
 ACT_NONE, ACT_RELU, ACT_LRELU = 0, 1, 2
@@ -10,13 +11,11 @@ EPS, MOM, SLOPE = 1e-5, 0.1, 0.2
 
 
 def _i64(be, v):
-    if be.name == "emu":
-        return np.array([v], dtype=np.int64)
-    return be.torch.tensor([v], dtype=be.torch.int64, device=be.device)
+    return be.dev_i64(np.array([v], dtype=np.int64))
 
 
 def _i64_value(be, t):
-    return int(np.asarray(t)[0]) if be.name == "emu" else int(t.item())
+    return int(be.np(t)[0])
 
 
 def _act(z, act):
@@ -258,6 +257,7 @@ def case_batchnorm_segments(be, N=6, C=5, H=7, W=9, S=3, act=ACT_LRELU, seed=2):
     assert np.array_equal(np.asarray(be.np(gw), dtype=np.float32), tw) and np.array_equal(np.asarray(be.np(gb), dtype=np.float32), tb)
 
 
+@both_poisons
 def case_batchnorm_dropout_and_max(be, N=2, C=128, H=6, W=10, seed=3, act=ACT_RELU):
     """dropout fused into the BatchNorm pass == BatchNorm followed by nemar_dropout with the same (p, seed, offset), bit for bit, forward and
     backward; the published max words == nemar_absmax_samples of the output; two identical calls are bit-identical"""

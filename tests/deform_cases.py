@@ -104,7 +104,8 @@ def ref_meter(pred, mode, g):
 # ---- drivers ------------------------------------------------------------------------------------------------------------------------------
 def run_field(be, params, B, Hc, Wc, gh, gw):
     d_g = be.full((B, 2, Hc, Wc), np.nan)
-    be.lib.deform_field(be.ptr(be.dev(params)), be.ptr(d_g), B, Hc, Wc, gh, gw, be.stream)
+    d_p = be.dev(params)
+    be.lib.deform_field(be.ptr(d_p), be.ptr(d_g), B, Hc, Wc, gh, gw, be.stream)
     return d_g
 
 

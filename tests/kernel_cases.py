@@ -2,6 +2,7 @@
 exactly as include/nemar_hip.h declares it and compares with oracle/ops_np.py evaluated in float64."""
 import numpy as np
 
+from backends import both_poisons
 from oracle import ops_np as O
 
 GRID_EXPLICIT, GRID_UNET, GRID_AFFINE = 0, 1, 2
@@ -86,7 +87,7 @@ def case_grid_sample(be, mode, N, C, H, W, Ho, Wo, scale, seed=0, need_gin=True,
                                be.ptr(d_gsrc), int(accumulate), N, C, H, W, Ho, Wo, be.ptr(ws), wsb, be.stream)
         if workspace:
             zb = be.lib.grid_sample_bwd_zeroed_bytes(N, C, H, W)
-            assert not np.any(be.np(ws)[:zb // 4]), "grid_sample_bwd must return the accumulator part of its workspace zero-filled"
+            assert not np.any(be.raw(ws)[:zb]), "grid_sample_bwd must return the accumulator part of its workspace zero-filled"
             if rep == 0:
                 first = (None if d_gin is None else be.np(d_gin).copy(), be.np(d_gsrc).copy())
             elif not atomic and H == Ho and W == Wo and C <= 4:      # bitwise reproducible (gather + fixed-point path)
@@ -395,6 +396,7 @@ def case_conv_split16(be, N, C, H, W, K, pad_mode, dgrad, seed=0, R=3):
             case_conv_fwd(be, N, C, 0, H, W, K, 3, 1, 1, pad_mode, act=O.ACT_NONE, seed=seed)
 
 
+@both_poisons
 def case_conv_split16_dynamic_range(be, what, N=3, C=128, H=8, W=32, K=128, seed=0):
     """The fp16 x 3 route of the wide layers (csrc/conv_split16*.hip) on adversarial magnitudes, through the C ABI: the scale is per
     SAMPLE, so every sample keeps fp32-class accuracy relative to its own magnitude.  what: 'samples' = per-sample magnitudes
@@ -490,17 +492,18 @@ def case_conv_split16_dynamic_range(be, what, N=3, C=128, H=8, W=32, K=128, seed
     assert np.all(np.abs(gw - want_gw) <= lim), ("wgrad", float((np.abs(gw - want_gw) / lim).max()))
 
 
-def case_absmax_and_hint(be, seed=0):
+@both_poisons
+def case_absmax_and_hint(be, seed=0, sizes=((1, 0), (1027, 0), (40003, 1), (300000, 0)), with_hint=True, samples=(3, 1000)):
     """nemar_absmax against numpy, odd sizes and an unaligned view; and a
     split-16 forward with the hint registered gives bit-identical results to one that runs its own max pass."""
     rng = np.random.default_rng(seed)
-    for n, off in ((1, 0), (1027, 0), (40003, 1), (300000, 0)):
+    for n, off in sizes:
         a = (rng.standard_normal(n + off) * 10.0 ** rng.uniform(-6, 3)).astype(np.float32)
         d = be.dev(a)
         word = be.bytes_buf(4)
-        view = d[off:]
+        view = be.sub(d, off, n + off)
         be.lib.absmax(be.ptr(view), n, be.ptr(word), be.stream)
-        got = np.asarray(be.np(word), dtype=np.float32)[:1].view(np.uint32)[0]
+        got = be.raw(word).view(np.uint32)[0]
         want = np.abs(a[off:]).max().astype(np.float32).view(np.uint32)
         assert int(got) == int(want), (n, off, hex(int(got)), hex(int(want)))
     N, C, H, W, K = 1, 16, 8, 32, 128
@@ -509,7 +512,7 @@ def case_absmax_and_hint(be, seed=0):
     d_x, d_w = be.dev(x), be.dev(w)
     outs = []
     with scratch_arena(be, split16_scratch(be, N, H, W, K, C, 3, 3, 1, 1)):
-        for hint in (False, True):
+        for hint in ((False, True) if with_hint else ()):
             d_y = be.full((N, K, H, W), np.nan)
             wsb = be.lib.conv2d_fwd_workspace(N, H, W, K, C, 3, 3, 1, 1)
             cws = be.bytes_buf(wsb)
@@ -522,14 +525,17 @@ def case_absmax_and_hint(be, seed=0):
             if hint:
                 be.lib.absmax_hint(be.ptr(d_x), None, 0)
             outs.append(be.np(d_y))
-    assert np.array_equal(outs[0], outs[1])
+    assert not with_hint or np.array_equal(outs[0], outs[1])
     # per-sample words: finite maxima only (an infinity / NaN does not take part)
-    a = (rng.standard_normal((3, 1000)) * np.array([[1e-5], [1.0], [300.0]])).astype(np.float32)
-    a[1, 7] = np.inf
-    a[2, 9] = np.nan
-    words = be.bytes_buf(12)
-    be.lib.absmax_samples(be.ptr(be.dev(a)), 3, 1000, be.ptr(words), be.stream)
-    got = np.asarray(be.np(words), dtype=np.float32)[:3].view(np.uint32)
+    S, per = samples
+    a = (rng.standard_normal((S, per)) * np.resize(np.array([1e-5, 1.0, 300.0]), S).reshape(S, 1)).astype(np.float32)
+    if per > 9 and S > 2:
+        a[1, 7] = np.inf
+        a[2, 9] = np.nan
+    words = be.bytes_buf(4 * S)
+    d_a = be.dev(a)
+    be.lib.absmax_samples(be.ptr(d_a), S, per, be.ptr(words), be.stream)
+    got = be.raw(words).view(np.uint32)
     fin = np.where(np.isfinite(a), np.abs(a), 0).max(axis=1).astype(np.float32).view(np.uint32)
     assert list(map(int, got)) == list(map(int, fin))
 
@@ -543,6 +549,7 @@ def case_conv_split16_wgrad(be, N, C, H, W, K, pad_mode, seed=0, R=3):
         case_conv_bwd_weight(be, N, C, 0, H, W, K, R, 1, 1, pad_mode, seed=seed)
 
 
+@both_poisons
 def case_conv_split16_dual_gy(be, N, C, H, W, K, pad_mode, seed=0):
     """The data-gradient call of a wide 3x3 layer leaves the weight gradient's operand planes of gy behind (nemar_conv_extras.gy_planes_out ->
     .src2_planes, csrc/conv_split16_wgrad.hip split_dual_kernel: gy is read and split once for both calls).  Both gradients must be
@@ -715,6 +722,7 @@ def case_instnorm(be, N, C, H, W, act, residual=False, seed=0):
     _assert_close(be.np(d_gx), want_gx, atol=3e-5 * np.abs(want_gx).max(), rtol=1e-4, what="instnorm_bwd")
 
 
+@both_poisons
 def case_producer_max_words(be, seed=0):
     """InstanceNorm forward / backward and dropout with the per-sample maximum of their output as a by-product (the words the fp16 x 3
     convolutions scale by): same outputs as the plain entry points, words == numpy's per-sample finite maximum."""
@@ -726,7 +734,7 @@ def case_producer_max_words(be, seed=0):
     d_x, d_res, d_gy = be.dev(x), be.dev(res), be.dev(gy)
 
     def words_of(buf):
-        return list(map(int, np.asarray(be.np(buf), dtype=np.float32)[:N].view(np.uint32)))
+        return list(map(int, be.raw(buf)[:4 * N].view(np.uint32)))
 
     def want(a):
         return list(map(int, np.abs(a.reshape(N, -1)).max(axis=1).astype(np.float32).view(np.uint32)))
@@ -771,6 +779,7 @@ def case_producer_max_words(be, seed=0):
     assert np.array_equal(be.np(y0), be.np(y1)) and words_of(w) == want(a)
 
 
+@both_poisons
 def case_conv_ex(be, N=3, C=128, H=8, W=32, K=128, seed=0):
     """nemar_conv2d_*_ex: arena and max words passed with the call == the registered arena / hints, bit for bit, on the same route."""
     import ctypes as C_
@@ -825,11 +834,10 @@ def case_conv_ex(be, N=3, C=128, H=8, W=32, K=128, seed=0):
         assert np.array_equal(a, b), what
 
 
-def case_step_params_in_device_memory(be, seed=0):
+def case_step_params_in_device_memory(be, seed=0, n=5003):
     """What a captured hipGraph needs: nemar_adam_step_dev (the two step-dependent scalars read from device memory) == nemar_adam_step,
     and a dropout launch with base word b and offset k == the launch with offset b + k and no base — bit for bit."""
     rng = np.random.default_rng(seed)
-    n = 5003
     p0 = rng.standard_normal(n).astype(np.float32)
     g = (rng.standard_normal(n) * 0.1).astype(np.float32)
     m0 = (rng.standard_normal(n) * 0.01).astype(np.float32)
@@ -867,6 +875,7 @@ def _decode_planes(raw, N, C, H, W):
     return a.transpose(0, 1, 2, 5, 3, 4).reshape(2, N, C, H + 4, W + 4)
 
 
+@both_poisons
 def case_instnorm_planes(be, act, use_residual, drop_p, N=2, C=16, H=6, W=8, seed=0):
     """InstanceNorm (+ activation, + dropout, + residual) that also writes its output as the fp16 x 3 planes of the following 3x3
     reflect convolution (csrc/norm_planes.hip): fp32 output / statistics against float64, the dropout mask against nemar_dropout's,
@@ -925,6 +934,7 @@ def case_instnorm_planes(be, act, use_residual, drop_p, N=2, C=16, H=6, W=8, see
     assert np.all(np.abs(hi[:, :, :H + 2, :W + 2] - ypad) <= 2.0 ** -11 * np.abs(ypad) + 2.0 ** -24 / scale.reshape(N, 1, 1, 1))
 
 
+@both_poisons
 def case_conv_from_producer_planes(be, N=3, C=128, H=8, W=32, K=128, seed=0):
     """A wide 3x3 reflect convolution that takes its operand planes from the InstanceNorm pass that produced its input
     (nemar_planes_hint + the bound words as nemar_absmax_hint): same accuracy bound as with its own max + split passes; and the
@@ -989,6 +999,7 @@ def _dgrad_plane_content(g, reflect):
     return out
 
 
+@both_poisons
 def case_resblock_planes_chain(be, pad_mode, act, drop_p, N=2, C=128, H=8, W=32, seed=0, producers_only=False):
     """The producer-fused chain of a ResnetBlock convolution (round 6): the InstanceNorm pass in front writes the weight gradient's X
     planes too (nemar_instnorm_fwd_planes wgrad_planes), the InstanceNorm BACKWARD behind writes the operand planes of both gradient
@@ -1203,11 +1214,15 @@ def case_resblock_planes_chain(be, pad_mode, act, drop_p, N=2, C=128, H=8, W=32,
         lib.tune(39, 8)
 
 
-def case_pointwise(be, seed=0):
+POOL_SHAPES = ((8, 10), (7, 9), (2, 2))
+BILINEAR_SHAPES = ((4, 5, 8, 10), (2, 2, 4, 4), (1, 3, 2, 6), (8, 12, 4, 6), (8, 12, 2, 3), (5, 7, 9, 4), (9, 12, 3, 2), (6, 8, 3, 2))
+
+
+@both_poisons
+def case_pointwise(be, seed=0, flat_n=(1027,), pool=POOL_SHAPES, bilinear=BILINEAR_SHAPES):
     rng = np.random.default_rng(seed)
     # act_bwd
-    for act in (O.ACT_RELU, O.ACT_LRELU, O.ACT_TANH):
-        n = 1027
+    for act, n in ((a, n) for a in (O.ACT_RELU, O.ACT_LRELU, O.ACT_TANH) for n in flat_n):
         pre = rng.standard_normal(n).astype(np.float32)
         y = O.act_fwd(pre.astype(np.float64), act).astype(np.float32)
         gy = rng.standard_normal(n).astype(np.float32)
@@ -1220,7 +1235,7 @@ def case_pointwise(be, seed=0):
         be.lib.act_fwd(be.ptr(d_pre), be.ptr(d_out), n, act, 0.2, be.stream)
         _assert_close(be.np(d_out), O.act_fwd(pre.astype(np.float64), act), atol=1e-6, rtol=1e-6, what="act_fwd")
     # maxpool (even, odd sizes; ties)
-    for (H, W) in ((8, 10), (7, 9), (2, 2)):
+    for (H, W) in pool:
         x = rng.integers(-3, 4, (2, 3, H, W)).astype(np.float32)     # many exact ties
         want, _ = O.maxpool2_fwd(x.astype(np.float64))
         Ho, Wo = H // 2, W // 2
@@ -1238,8 +1253,7 @@ def case_pointwise(be, seed=0):
         be.lib.maxpool2_bwd(be.ptr(d_x), be.ptr(d_gy), be.ptr(d_add), be.ptr(d_gx), 6, H, W, be.stream)
         _assert_close(be.np(d_gx), want_g + add, atol=1e-6, what="maxpool2_bwd+addend")
     # bilinear: 2x up (gather backward), /2 and /4 down, arbitrary
-    for (H, W, Ho, Wo) in ((4, 5, 8, 10), (2, 2, 4, 4), (1, 3, 2, 6), (8, 12, 4, 6), (8, 12, 2, 3), (5, 7, 9, 4), (9, 12, 3, 2),
-                           (6, 8, 3, 2)):
+    for (H, W, Ho, Wo) in bilinear:
         x = rng.standard_normal((2, 2, H, W)).astype(np.float32)
         want = O.bilinear_resize_fwd(x.astype(np.float64), Ho, Wo)
         d_y = be.full((2, 2, Ho, Wo), np.nan)
@@ -1254,13 +1268,16 @@ def case_pointwise(be, seed=0):
         _assert_close(be.np(d_gx), want_g, atol=5e-6, what="bilinear_bwd %s" % ((H, W, Ho, Wo),))
 
 
-def case_concat_and_add(be, seed=0):
+CONCAT_CASES = (((7200, 7200, 7200), None), ((7200, 7200, 7200), 1), ((1027, 5, 4096), None), ((48,), None), ((1030,), 0),
+                ((64, 64, 64, 64, 64, 64, 64, 64), 7), ((3, 1), 0))
+
+
+def case_concat_and_add(be, seed=0, concat=CONCAT_CASES, add_sizes=(4, 48, 1027, 65536 + 3)):
     """nemar_concat_pieces (batch concatenation / the gradient of batch slices, a NULL piece = zeros; 16-byte and scalar forms) and
     nemar_add2 (the sum of two consumers' gradients; aliasing the output) against numpy — bit for bit: copies and one fp32 add."""
     import ctypes
     rng = np.random.default_rng(seed)
-    for counts, null in (((7200, 7200, 7200), None), ((7200, 7200, 7200), 1), ((1027, 5, 4096), None), ((48,), None), ((1030,), 0),
-                         ((64, 64, 64, 64, 64, 64, 64, 64), 7), ((3, 1), 0)):
+    for counts, null in concat:
         pieces = [rng.standard_normal(c).astype(np.float32) for c in counts]
         devs = [None if i == null else be.dev(q) for i, q in enumerate(pieces)]
         want = np.concatenate([np.zeros(c, np.float32) if i == null else q for i, (q, c) in enumerate(zip(pieces, counts))])
@@ -1270,7 +1287,7 @@ def case_concat_and_add(be, seed=0):
         be.lib.concat_pieces(ptrs, cnts, len(counts), be.ptr(d_out), be.stream)
         got = be.np(d_out)
         assert got.shape == want.shape and (got == want.astype(np.float64)).all(), "concat_pieces %r null=%r" % (counts, null)
-    for n in (4, 48, 1027, 65536 + 3):
+    for n in add_sizes:
         a, b = rng.standard_normal(n).astype(np.float32), rng.standard_normal(n).astype(np.float32)
         want = (a + b).astype(np.float64)
         d_a, d_b, d_o = be.dev(a.copy()), be.dev(b), be.full((n,), np.nan)
@@ -1300,15 +1317,15 @@ def case_dropout(be, n=40003, p=0.5):
     assert abs(np.corrcoef(k[:-1], k[1:])[0, 1]) < 0.03
 
 
-def case_losses(be, seed=0):
+def case_losses(be, seed=0, sizes=(7, 5000), gan_bwd_atol=1e-9):
     rng = np.random.default_rng(seed)
     wsb = be.lib.loss_workspace()
     ws = be.bytes_buf(wsb)
     gs = be.dev(np.array([0.5], dtype=np.float32))
-    for n in (7, 5000):
+    for n in sizes:
         a = rng.standard_normal(n).astype(np.float32)
         b = rng.standard_normal(n).astype(np.float32)
-        b[:3] = a[:3]                                  # sign(0) = 0
+        b[:3] = a[:3]                                  # sign(0) = 0 (every element where n <= 3)
         for bb in (b, None):
             b64 = bb.astype(np.float64) if bb is not None else np.zeros(n)
             loss = be.full((1,), 2.0)
@@ -1329,7 +1346,7 @@ def case_losses(be, seed=0):
                               rtol=1e-5, what="gan_loss_fwd " + name)
                 gx = be.full((n,), np.nan)
                 be.lib.gan_loss_bwd(be.ptr(d_x), n, mode, real, be.ptr(gs), 0.5, be.ptr(gx), be.stream)
-                _assert_close(be.np(gx), 0.25 * O.gan_loss_bwd(x.astype(np.float64), bool(real), name), atol=1e-9,
+                _assert_close(be.np(gx), 0.25 * O.gan_loss_bwd(x.astype(np.float64), bool(real), name), atol=gan_bwd_atol,
                               rtol=2e-5, what="gan_loss_bwd " + name)
 
 
@@ -1351,13 +1368,13 @@ def case_adam(be, n=3001, steps=3, seed=0):
     _assert_close(be.np(d_v), v64, atol=1e-7 * np.abs(v64).max(), rtol=1e-6, what="adam v")
 
 
-def case_crop_flip_normalize(be, seed=0):
+def case_crop_flip_normalize(be, seed=0, M=5, C=3, H=11, W=14, Hc=8, Wc=9, params=((3, 0, 0, 0), (0, 3, 5, 1), (4, 2, 1, 1), (1, 1, 4, 0))):
     """Input-pipeline augmentation: crop + flip + Normalize(0.5, 0.5) of a resident pool (numpy restatement of the reference's
     get_transform chain, data/base_dataset.py:81-112)."""
     rng = np.random.default_rng(seed)
-    M, C, H, W, Hc, Wc, B = 5, 3, 11, 14, 8, 9, 4
+    params = np.array(params, dtype=np.int32)
+    B = len(params)
     pool = rng.uniform(0, 1, (M, C, H, W)).astype(np.float32)
-    params = np.array([[3, 0, 0, 0], [0, 3, 5, 1], [4, 2, 1, 1], [1, 1, 4, 0]], dtype=np.int32)
     want = np.zeros((B, C, Hc, Wc))
     for b, (i, y0, x0, flip) in enumerate(params):
         crop = pool[i, :, y0:y0 + Hc, x0:x0 + Wc].astype(np.float64)
