@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 604 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 605 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -423,6 +423,28 @@ int nemar_crop_flip_deform_normalize(const float* pool, const int* params, const
 size_t nemar_registration_error_workspace(int N, int H, int W);
 int nemar_registration_error(const float* pred, int grid_mode, const float* g, float* out, void* workspace, size_t ws_bytes,
                              int N, int H, int W, void* stream);
+
+/* Registration at any resolution (not a call site of the reference, which warps at the network's own size only): the STN's prediction
+ * applied to an image of another size in one pass.  It fuses the reference's upsampling of a coarse deformation to the output size
+ * with the warp itself — F.interpolate(offsets, (Ho,Wo), 'bilinear', align_corners=False) then F.grid_sample(in, identity + offsets),
+ * reference models/stn/unet_stn.py:139-141,165-174 — and F.affine_grid(theta, (Ho,Wo)) + F.grid_sample, models/stn/affine_stn.py:122,128:
+ * the sampling grid is in normalised coordinates, so the same prediction describes the transformation at every size.
+ *   NEMAR_GRID_UNET    pred = offsets [N,2,hf,wf]; grid(h,w) = linspace(-1,1,Wo)[w] + R(pred)[0,h,w], linspace(-1,1,Ho)[h] + R(pred)[1,h,w],
+ *                      R = the bilinear resize to (Ho,Wo) whenever (hf,wf) != (Ho,Wo), evaluated in registers (never written), and the
+ *                      identity when the sizes are equal.  (The "only if BOTH dims differ" rule of the reference is the caller's.)
+ *   NEMAR_GRID_AFFINE  pred = dtheta [N,6]; the grid is affine_grid(dtheta + I, align_corners=False) at (Ho,Wo); hf, wf are ignored.
+ *   NEMAR_GRID_EXPLICIT is NEMAR_EINVAL (a materialised grid has one resolution).
+ * sample_mode: NEMAR_SAMPLE_BILINEAR = F.grid_sample(..., 'bilinear', 'zeros', align_corners=False), bit for bit what
+ * nemar_bilinear_fwd + nemar_grid_sample_fwd give; NEMAR_SAMPLE_NEAREST = F.grid_sample(..., 'nearest', 'zeros', align_corners=False):
+ * the unnormalised position rounded half-to-even, zero where that texel is outside the source — for label maps, whose class ids must
+ * not be blended.  in [N,C,Hs,Ws] -> out [N,C,Ho,Wo]; the source size is free.
+ * Alignment: in, pred and out need 4-byte alignment only (anything else is NEMAR_EINVAL): the kernel handles one pixel per lane, so odd
+ * widths and views off the 16-byte grid take the same route as everything else.  (A 16-byte-store route exists in the measurement build,
+ * nemar_hip_ab.h key 44; profiles/register_fullres.txt has the two side by side.) */
+#define NEMAR_SAMPLE_BILINEAR 0
+#define NEMAR_SAMPLE_NEAREST 1
+int nemar_warp_resampled_fwd(const float* in, const float* pred, int grid_mode, int sample_mode, float* out,
+                             int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

@@ -51,7 +51,9 @@ extern "C" {
  *      halo (0, default = one workgroup per (tile, class): the fused form measured 10-30 % slower, csrc/conv_s16g.hip; 1 = where the grid
  *      keeps min(192, key 41) workgroups; 2 = 1 and a four-class problem that cannot fuse leaves the route: tests)
  *   43 stride-1 reflect data gradients of tiny maps on the exact-fp32 kernels: one split launch over the padded domain + a sum-and-fold pass
- *      (1, default) / interior + border-ring launches with their sums and a gather (0) */
+ *      (1, default) / interior + border-ring launches with their sums and a gather (0)
+ *   44 nemar_warp_resampled_fwd: 4 consecutive pixels per lane and 16-byte stores where Wo % 4 == 0 and out is 16-byte aligned (1) / one pixel
+ *      per lane everywhere (0, default: the 16-byte form takes 27 - 37 % longer, profiles/register_fullres.txt) */
 int nemar_tune(int key, int value);
 int nemar_tune_ptr(void* timeline_buffer);   /* device buffer for per-stage cycle stamps (tools/timeline_*.py), NULL = off */
 /* grad_input variant for A/B measurements: 0 (default) = gather + fixed point (needs the workspace), 1 = fp32 atomics through an

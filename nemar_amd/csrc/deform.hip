@@ -216,11 +216,7 @@ __device__ __forceinline__ void reg_block_store(const RegAcc& a, unsigned* __res
 }
 
 // x -> S(x): the pixel position the warp kernel samples for grid_src values (sx, sy) held in registers, at output pixel (h, w)
-struct RegSrc {
-    float sx, sy;
-    __device__ __forceinline__ float x() const { return sx; }
-    __device__ __forceinline__ float y() const { return sy; }
-};
+// (RegSrc: warp_grid.h)
 template <int MODE>
 __device__ __forceinline__ void warp_position(float sx, float sy, int h, int w, int H, int W, const float* th, float& ix, float& iy) {
     float gx, gy;

@@ -8,6 +8,7 @@
 //   dropout        nn.Dropout(0.5) — reference models/networks.py:427-428 (ON by default, nemar_model.py:102)
 #include "common.h"
 #include "max_words.h"
+#include "resize_taps.h"   // Tap1D / tap1d / resize_blend (shared with register.hip)
 
 namespace {
 
@@ -118,19 +119,7 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(const float* __restri
 }
 
 // ---- bilinear resize, align_corners=False ---------------------------------------------------------------------------
-struct Tap1D { int i0, i1; float l0, l1; };
-__device__ __forceinline__ Tap1D tap1d(int d, int n_in, float scale) {
-    // s = max((d + 0.5) * in/out - 0.5, 0); i0 = floor(s); i1 = min(i0 + 1, in - 1)
-    float s = ((float)d + 0.5f) * scale - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    Tap1D t;
-    t.i0 = min((int)s, n_in - 1);
-    t.i1 = min(t.i0 + 1, n_in - 1);
-    t.l1 = s - (float)t.i0;
-    t.l0 = 1.f - t.l1;
-    return t;
-}
-
+// (source index / weights of one axis and the four-tap sum: resize_taps.h)
 __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W,
                                                            int Ho, int Wo, float sh, float sw, long long total) {
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
@@ -141,9 +130,7 @@ __global__ __launch_bounds__(256) void bilinear_fwd_kernel(const float* __restri
         const long long nc = t / Ho;
         const Tap1D th = tap1d(ho, H, sh), tw = tap1d(wo, W, sw);
         const float* p = x + nc * (long long)H * W;
-        const float top = p[th.i0 * W + tw.i0] * tw.l0 + p[th.i0 * W + tw.i1] * tw.l1;
-        const float bot = p[th.i1 * W + tw.i0] * tw.l0 + p[th.i1 * W + tw.i1] * tw.l1;
-        y[idx] = top * th.l0 + bot * th.l1;
+        y[idx] = resize_blend(p[th.i0 * W + tw.i0], p[th.i0 * W + tw.i1], p[th.i1 * W + tw.i0], p[th.i1 * W + tw.i1], tw, th);
     }
 }
 

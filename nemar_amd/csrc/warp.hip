@@ -13,26 +13,9 @@
 // offset loads and output stores are 16 B/lane coalesced when Wo % 4 == 0; the four-corner gathers hit
 // L1/L2 (each source texel is touched by ~4 neighbouring lanes in the near-identity regime).
 #include "common.h"
-#include "warp_grid.h"   // grid modes, linspace / affine base, make_grid, sample_position (shared with deform.hip)
+#include "warp_grid.h"   // grid modes, linspace / affine base, make_grid, sample_position, locate (shared with deform.hip, register.hip)
 
 namespace {
-
-struct Sample {
-    int x0, y0;
-    float tx, ty;  // ix - x0, iy - y0
-};
-__device__ __forceinline__ Sample locate(float gx, float gy, int W, int H) {
-    float ix, iy;
-    sample_position(gx, gy, W, H, ix, iy);
-    const float fx = floorf(ix), fy = floorf(iy);
-    Sample s;
-    // clamp far-out-of-range coordinates before the int conversion (all four corners are OOB anyway)
-    s.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
-    s.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-    s.tx = ix - fx;
-    s.ty = iy - fy;
-    return s;
-}
 
 // ---- forward ---------------------------------------------------------------------------------------
 template <int MODE, int VEC>

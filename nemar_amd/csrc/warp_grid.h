@@ -61,6 +61,13 @@ struct GridSrc {
     __device__ __forceinline__ float x() const { return p[0]; }
     __device__ __forceinline__ float y() const { return p[step]; }
 };
+// the two grid_src values of a pixel held in registers (deform.hip: filled by 16-byte loads; register.hip: interpolated from a coarse field)
+struct RegSrc {
+    float sx, sy;
+    __device__ __forceinline__ float x() const { return sx; }
+    __device__ __forceinline__ float y() const { return sy; }
+};
+
 template <int MODE>
 __device__ __forceinline__ void make_grid(const float* __restrict__ gsrc, int n, int h, int w, int Ho, int Wo,
                                           const float* th, float& gx, float& gy) {
@@ -72,6 +79,24 @@ __device__ __forceinline__ void make_grid(const float* __restrict__ gsrc, int n,
 __device__ __forceinline__ void sample_position(float gx, float gy, int W, int H, float& ix, float& iy) {
     ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
     iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+}
+
+// the top-left corner of the 2 x 2 patch a normalised coordinate samples bilinearly, and the fractional position inside it
+struct Sample {
+    int x0, y0;
+    float tx, ty;  // ix - x0, iy - y0
+};
+__device__ __forceinline__ Sample locate(float gx, float gy, int W, int H) {
+    float ix, iy;
+    sample_position(gx, gy, W, H, ix, iy);
+    const float fx = floorf(ix), fy = floorf(iy);
+    Sample s;
+    // clamp far-out-of-range coordinates before the int conversion (all four corners are OOB anyway)
+    s.x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f);
+    s.y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+    s.tx = ix - fx;
+    s.ty = iy - fy;
+    return s;
 }
 
 }  // namespace

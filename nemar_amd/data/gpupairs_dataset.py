@@ -141,17 +141,37 @@ class GpuPairsDataset(BaseDataset):
             nh, nw = int(round(h / 4) * 4), int(round(w / 4) * 4)
         else:
             nh, nw = h, w
-        if (nh, nw) == (h, w):
+        return self.resize_to(pool, nh, nw)
+
+    @staticmethod
+    def resize_to(pool, nh, nw):
+        """pool [M,C,H,W] in [0, 1] at nh x nw: bicubic, antialiased, clamped (untouched when it has that size already)"""
+        if (nh, nw) == tuple(pool.shape[2:]):
             return pool
         out = torch.nn.functional.interpolate(pool, size=(nh, nw), mode='bicubic', align_corners=False, antialias=True)
         return out.clamp_(0.0, 1.0).contiguous()
 
+    @staticmethod
+    def whole_images(pool, indices):
+        """the images `indices` of pool [M,C,H,W] in [0, 1], whole and unflipped, as the network takes them: Normalize(0.5, 0.5) by the
+        launch batch() uses, with the identity crop -> [len(indices),C,H,W] in [-1, 1]"""
+        M, C, H, W = pool.shape
+        params = torch.tensor([(i, 0, 0, 0) for i in indices], dtype=torch.int32).to(pool.device)
+        y = torch.empty((len(indices), C, H, W), dtype=torch.float32, device=pool.device)
+        ops.L.crop_flip_normalize(ctypes.c_void_p(pool.data_ptr()), ctypes.c_void_p(params.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+                                  M, len(indices), C, H, W, H, W, 1.0, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+        return y
+
     def _load(self, path):
+        return self.load_pool(path, self.device)
+
+    @staticmethod
+    def load_pool(path, device):
         a = np.load(path)
         if a.ndim == 4 and a.shape[-1] == 3:
             a = a.transpose(0, 3, 1, 2)
         scale = 1.0 / 255.0 if a.dtype == np.uint8 else 1.0
-        t = torch.from_numpy(np.ascontiguousarray(a)).to(self.device, torch.float32) * scale
+        t = torch.from_numpy(np.ascontiguousarray(a)).to(device, torch.float32) * scale
         return t.contiguous(), ['%s[%d]' % (path, i) for i in range(t.shape[0])]
 
     def __len__(self):

@@ -202,6 +202,39 @@ class NEMARModel(BaseModel):
         cols[2] = rows[:, 2].max()
         return registration_summary(cols.tolist(), self.gt_field.size(0) * self.gt_field.size(2) * self.gt_field.size(3))
 
+    def register(self, full_A, full_B=None, labels_A=None, translate=True):
+        """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the
+        network's resolution) predicted: the sampling grid is in normalised coordinates, so the prediction holds at every size, and the
+        warp kernel resizes a dense field on the fly (ops.warp_resampled).  full_A [N,C,H,W] is modality A of the same N pairs at any
+        size; the warp is linear, so 'registered_A' comes back in whatever value range full_A has, but netT reads it as a network input:
+        pass it in [-1, 1] (what set_input takes) when `translate` is on.  Returns a dict: 'registered_A' (full_A warped bilinearly, at its
+        own size); 'fake_RT_B' (netT(full_A) warped, at that size too — a full-size generator pass, skipped with translate=False) only when
+        netT can run at full_A's size — the key is absent otherwise, nothing is resized; 'registered_labels_A' (labels_A
+        [N,*,H',W'] warped with nearest sampling: class ids are copied, never blended) when labels_A is given; 'offsets', the
+        network-resolution prediction itself (offsets [N,2,h,w] or dtheta [N,6]).  full_B is accepted for symmetry with set_input and is
+        not read: the prediction is made from the network-resolution pair."""
+        pred = self.netR.last_prediction()
+        if pred is None:
+            raise RuntimeError('register: no forward pass yet')
+        with torch.no_grad():
+            full_A = full_A.to(self.device, dtype=torch.float32).contiguous()
+            if full_A.size(0) != pred[0].size(0):
+                raise ValueError('register: %d images for a prediction of %d pairs' % (full_A.size(0), pred[0].size(0)))
+            out = {'registered_A': self.netR.apply(pred, [full_A])[0], 'offsets': pred[0]}
+            if translate and self._netT_runs_at(full_A.size(2), full_A.size(3)):
+                out['fake_RT_B'] = self.netR.apply(pred, [self.netT(full_A)])[0]
+            if labels_A is not None:
+                labels_A = labels_A.to(self.device, dtype=torch.float32).contiguous()
+                out['registered_labels_A'] = self.netR.apply(pred, [labels_A], sample='nearest')[0]
+        return out
+
+    def _netT_runs_at(self, h, w):
+        """netT is fully convolutional, but its strided levels must divide the size: two for the ResNet generators (a transposed
+        convolution doubles what a stride-2 convolution halved only for even sizes), `num_downs` for the U-Nets (their skips concatenate)"""
+        g = self.opt.netG
+        levels = networks._UNET_DOWNS.get(g, 2 if g in networks._RESNET_BLOCKS else None)
+        return levels is not None and h % (1 << levels) == 0 and w % (1 << levels) == 0 and min(h, w) >= (1 << levels)
+
     # ---- forward -------------------------------------------------------------------------------------------
     def forward(self):
         if not self._batched:

@@ -20,10 +20,19 @@ _FLAGS = (
     ('--stn_multires_reg', dict(type=int, default=1,
                                 help='unet only: apply the smoothness penalty at this many resolutions (1 = full resolution only)'), True),
 )
+
+
+def _flag(opt, name):
+    """opt.<name>, or the flag's default where the command line did not carry it (the train-only flags on a test command line: they
+    configure the regulariser and the initialisation, which inference does not use)"""
+    kw = next(kw for flag, kw, _ in _FLAGS if flag == '--' + name)
+    return getattr(opt, name, kw.get('default', False))
+
+
 _BUILDERS = {
     'affine': lambda a, b, h, w, opt: AffineSTN(a, b, h, w, opt.stn_cfg, opt.init_type),
-    'unet': lambda a, b, h, w, opt: UnetSTN(a, b, h, w, opt.stn_cfg, opt.init_type, opt.stn_bilateral_alpha,
-                                            not opt.stn_no_identity_init, opt.stn_multires_reg),
+    'unet': lambda a, b, h, w, opt: UnetSTN(a, b, h, w, opt.stn_cfg, opt.init_type, _flag(opt, 'stn_bilateral_alpha'),
+                                            not _flag(opt, 'stn_no_identity_init'), _flag(opt, 'stn_multires_reg')),
 }
 
 

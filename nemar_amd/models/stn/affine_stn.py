@@ -5,7 +5,7 @@ import torch.nn as nn
 
 from ... import ops
 from ..networks import LinearParams, Slots
-from .layers import DownBlock
+from .layers import DownBlock, prediction_tensor
 
 cfg_conv1_nf = {'A': 32, }
 cfg_mlp_nf = {'A': 256}
@@ -83,6 +83,12 @@ class AffineSTN(nn.Module):
 
     def warp(self, field, imgs):
         return ops.warp_affine(field, list(imgs))
+
+    def apply(self, field, imgs, out_hw=None, sample='bilinear'):
+        """The prediction applied at ANY resolution, for inference: `field` is what predict() returned or last_prediction(); each image
+        is sampled at out_hw (default: its own size) on affine_grid(theta) of that size (ops.warp_resampled).  sample='nearest' for
+        label maps.  No autograd."""
+        return ops.warp_resampled(prediction_tensor(field), ops.GRID_AFFINE, list(imgs), out_hw, sample)
 
     def fork_field(self, field, n_warps):
         """-> ([one theta handle per warp() call], the handle for regularization()) — ops.fork, as UnetSTN.fork_field"""

@@ -134,3 +134,16 @@ class DownBlock(nn.Module):
             else:
                 x = ops.max_pool2(x)
         return (x, skip) if self.skip else x
+
+
+def prediction_tensor(field):
+    """The tensor the warp kernels take, from any of the forms an STN hands its prediction around in: the tensor itself, the
+    `(tensor, grid mode)` pair of last_prediction(), AffineSTN.predict()'s dtheta, UnetSTN.predict()'s `(d, d_up)` (the field at the
+    network's size is the last one)."""
+    import torch
+    if torch.is_tensor(field):
+        return field
+    tensors = [f for f in field if torch.is_tensor(f)]
+    if not tensors:
+        raise TypeError('not an STN prediction: %r' % (field,))
+    return tensors[-1]

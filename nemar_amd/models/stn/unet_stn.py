@@ -15,7 +15,7 @@ typo); the low-res upsample branch fires only if BOTH dims differ (B3).
 import torch.nn as nn
 
 from ... import ops
-from .layers import Conv, DownBlock, ResnetTransformer
+from .layers import Conv, DownBlock, ResnetTransformer, prediction_tensor
 from .stn_losses import smoothness_loss
 
 sampling_align_corners = False
@@ -138,6 +138,12 @@ class UnetSTN(nn.Module):
 
     def warp(self, field, imgs):
         return ops.warp_unet(field[1], list(imgs))
+
+    def apply(self, field, imgs, out_hw=None, sample='bilinear'):
+        """The prediction applied at ANY resolution, for inference: `field` is what predict() returned or last_prediction() (the offsets
+        at the network's size, already past the reference's low-resolution branch); each image is sampled at out_hw (default: its own
+        size) with the field resized inside the warp kernel (ops.warp_resampled).  sample='nearest' for label maps.  No autograd."""
+        return ops.warp_resampled(prediction_tensor(field), ops.GRID_UNET, list(imgs), out_hw, sample)
 
     def fork_field(self, field, n_warps):
         """-> ([one field per warp() call], the field for regularization()): handles of the same tensors (ops.fork), so that the

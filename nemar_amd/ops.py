@@ -1682,6 +1682,36 @@ def grid_sample(img, grid):
     return _Warp.apply(grid, GRID_EXPLICIT, int(grid.shape[1]), int(grid.shape[2]), img)[0]
 
 
+SAMPLE_MODES = {"bilinear": 0, "nearest": 1}
+
+
+def warp_resampled(pred, grid_mode, imgs, out_hw, sample='bilinear'):
+    """The STN's prediction applied at another resolution (nemar_warp_resampled_fwd): pred = offsets [N,2,hf,wf] (GRID_UNET; resized
+    bilinearly to out_hw inside the kernel, never written) or dtheta [N,6] (GRID_AFFINE); every image [N,C,Hs,Ws] of `imgs` is sampled
+    at out_hw = (Ho, Wo) — or at its own size where out_hw is None — with F.grid_sample's 'bilinear' or 'nearest' (label maps) rule and
+    zero padding.  Returns the list of warped images.  An inference read-out like registration_error: inputs are detached, no autograd."""
+    if sample not in SAMPLE_MODES:
+        raise ValueError("warp_resampled: sample %r is not one of %s" % (sample, sorted(SAMPLE_MODES)))
+    if grid_mode not in (GRID_UNET, GRID_AFFINE):
+        raise ValueError("warp_resampled: grid_mode %r (GRID_UNET or GRID_AFFINE)" % (grid_mode,))
+    pred = _c(pred.detach())
+    N = pred.shape[0]
+    if not ((pred.dim() == 4 and pred.shape[1] == 2) if grid_mode == GRID_UNET else tuple(pred.shape) == (N, 6)):
+        raise ValueError("warp_resampled: prediction %s, expected [N,2,hf,wf] offsets or [N,6] dtheta" % (tuple(pred.shape),))
+    hf, wf = (int(pred.shape[2]), int(pred.shape[3])) if grid_mode == GRID_UNET else (0, 0)
+    outs, st = [], _stream()
+    for img in imgs:
+        img = _c(img.detach())
+        if img.dim() != 4 or img.shape[0] != N:
+            raise ValueError("warp_resampled: image %s for a prediction of %d samples" % (tuple(img.shape), N))
+        _, C, Hs, Ws = img.shape
+        Ho, Wo = (Hs, Ws) if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+        out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=img.device)
+        L.warp_resampled_fwd(_p(img), _p(pred), grid_mode, SAMPLE_MODES[sample], _p(out), N, C, Hs, Ws, hf, wf, Ho, Wo, st)
+        outs.append(out)
+    return outs
+
+
 # ---- known misalignment: ground-truth fields, the deforming input pipeline, the registration-error meter (no autograd: data and read-outs) ----
 def deform_field(params, B, Hc, Wc, gh, gw):
     """params [B, 6 + 2*gh*gw] (a11 a12 tx a21 a22 ty about the crop centre, then a [2,gh,gw] lattice of pixel displacements; gh = gw = 0:
