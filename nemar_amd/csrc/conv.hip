@@ -19,6 +19,7 @@
 // conv_wgrad.hip (wave-specialised) for everything whose gy planes are 16-byte chunkable, wgrad_kernel below for the rest.
 #include "common.h"
 #include "conv_exact.h"
+#include "conv_call.h"
 #include "conv_split16.h"
 #include "conv_s16g.h"
 #include "conv_k7.h"
@@ -60,7 +61,7 @@ using namespace nemar_exact;
 namespace {
 
 // key 20: 3x3 / stride-1 layers with >= 128 output channels run on the bf16 matrix pipe with three-way split operands
-// (conv_split16.hip) whenever the caller has registered a scratch arena large enough for the split source planes
+// (conv_split16.hip) whenever the call brings a scratch arena large enough for the split source planes
 static NEMAR_SWITCH(int, g_split16, 1);
 // key 23: the split-16 route needs work to amortise its extra launches (max pass, split pass, slab sum): layers below this many
 // million multiply-adds (default 2000 = 4 GFLOP, ~40 us on the exact-fp32 kernels) stay on those — BASELINE config 1's 32x32
@@ -71,6 +72,7 @@ static NEMAR_SWITCH(int, g_split16_variant, 4);   // key 21: 4 fp16 x 3 products
 // which kernel family served the last conv call of this thread (nemar_last_route; tests and tools): 0 exact-fp32 implicit GEMM,
 // 1 narrow (<= 4 channel) VALU kernels, 2 split-16 kernel of the wide residual-block layers, 3 general 16-bit-pipe kernels
 static thread_local int g_last_route = 0;
+static thread_local int g_last_gy_planes = 0;     // did the last nemar_conv2d_bwd_data_ex call of this thread fill gy_planes_out? (nemar_last_gy_planes)
 static NEMAR_SWITCH(int, g_config_epoch, 0);      // A/B build: bumped by every nemar_tune (routes and packed-weight formats may have changed)
 static NEMAR_SWITCH(int, g_k7, 1);               // key 33: the 7x7 stem / head layers (<= 4 channels on one side) on the 16-bit matrix pipe (conv_k7.hip)
 static NEMAR_SWITCH(int, g_s16g, 1);             // key 24: general layers on the 16-bit matrix pipe with the in-kernel operand split (conv_s16g.hip)
@@ -79,24 +81,9 @@ static NEMAR_SWITCH(int, g_s16g_wgrad_first, 0);  // key 26: 1 = the in-kernel-s
 static NEMAR_SWITCH(int, g_s16g_wgrad, 1);        // key 29: weight gradients on the in-kernel-split kernels (conv_s16g_wgrad.hip)
 static NEMAR_SWITCH(int, g_s16g_fold, 1);         // key 30: stride-1 reflect data gradients on the padded domain + fold
 static NEMAR_SWITCH(long long, g_s16g_min_mmac, 30);   // key 25: ... above this many million multiply-adds (tiny layers are launch-bound either way)
-static thread_local void* t_scratch = nullptr;        // nemar_conv2d_*_ex: this call's scratch arena (nemar_conv_extras.scratch)
-static thread_local size_t t_scratch_bytes = 0;
-static thread_local void* t_gy_planes_out = nullptr;  // bwd_data_ex: where the pass that splits gy also leaves the weight gradient's planes
-static thread_local size_t t_gy_planes_bytes = 0;
-static thread_local const void* t_src2_planes = nullptr;      // bwd_weight_ex: those planes
-static thread_local const void* t_x_wplanes = nullptr;        // bwd_weight_ex: the X planes of x a forward producer wrote (extras.src_planes)
-static thread_local const float* t_addend = nullptr;          // bwd_data_ex: tensor added to gx0 in the epilogue (extras.addend)
-static thread_local void* t_out_max = nullptr;                // bwd_data_ex: per-sample max |gx0| words (extras.out_max_words)
-static thread_local int t_fused_epilogue = 0;                 // did the last bwd_data_ex call honour them?
-static thread_local int t_bias_rode = 0;                       // ... and did the call reduce them (the wide route)?
-static thread_local const float* t_bias_partials = nullptr;   // bwd_weight_ex: per-plane sums of gy [N, K] (extras.bias_partials)
-static thread_local int t_addend_done = 0;                    // ... or at least the addend (the fold pass of a small reflect layer: nemar_conv2d_bwd_data_addend_ok)
 static NEMAR_SWITCH(int, g_split_act, 1);          // key 36: reduction-split forward layers with a fused ReLU / LeakyReLU (activation in the sum pass)
 static NEMAR_SWITCH(int, g_fold_small, 1);         // key 43: stride-1 reflect data gradients of tiny maps on the exact route: padded domain + sum-and-fold pass
 static NEMAR_SWITCH(int, g_dual_gy, 1);            // key 35: the data-gradient call's split pass also writes the weight gradient's gy planes
-static thread_local int t_gy_planes_written = 0;      // did the last bwd_data_ex call on this thread fill gy_planes_out?
-#define g_scratch t_scratch
-#define g_scratch_bytes t_scratch_bytes
 static NEMAR_SWITCH(int, g_reflect_aux, 1);    // tuning switch (key 8): 3x3 reflect data gradient folds the border into the main launch (1) / ring launch (0)
 static NEMAR_SWITCH(int, g_deterministic, 1);  // tuning switch (key 14): 1 = split reductions go through per-split slabs summed in order (bitwise
                                  // reproducible backward pass), 0 = fp32 atomics in the weight / bias gradients (round-1 scheme)
@@ -858,9 +845,10 @@ NEMAR_API size_t nemar_conv2d_fwd_workspace(int N, int H, int W, int K, int C, i
     return sizeof(float) * fwd_layout(N, H, W, K, C, R, S, stride, pad).total;
 }
 
-NEMAR_API int nemar_conv2d_fwd(const float* x0, int C0, const float* x1, int C1, const float* w, const float* bias,
-                               float* y, int N, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode,
-                               int act, float slope, void* workspace, size_t ws_bytes, int prepacked, void* stream) {
+// Honours call.scratch, .src_max and .src_planes (the wide route)
+static int conv2d_fwd(ConvCall& call, const float* x0, int C0, const float* x1, int C1, const float* w, const float* bias,
+                      float* y, int N, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode,
+                      int act, float slope, void* workspace, size_t ws_bytes, int prepacked, void* stream) {
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(x0 && w && y && workspace, "conv2d_fwd: null pointer");
     NEMAR_REQUIRE(C0 > 0 && C1 >= 0 && (C1 == 0 || x1), "conv2d_fwd: bad channel split %d+%d", C0, C1);
@@ -913,10 +901,10 @@ NEMAR_API int nemar_conv2d_fwd(const float* x0, int C0, const float* x1, int C1,
         const int mode = pad_mode == BORDER_REFLECT ? SPLIT16_REFLECT : SPLIT16_ZERO;
         if (g_split16 && C1 == 0 && act == ACT_NONE && split16_worth_it(N, OH, OW, K, C, R, S) &&
             nemar_split16_eligible(N, H, W, K, C, R, S, stride, pad, mode, g_split16_variant) &&
-            g_scratch && g_scratch_bytes >= nemar_split16_scratch_total(N, H, W, K, C, OH, OW)) {
+            call.scratch && call.scratch_bytes >= nemar_split16_scratch_total(N, H, W, K, C, OH, OW)) {
             if (!prepacked) nemar_split16_pack(w, workspace, K, C, R, 0, g_split16_variant, st);
-            nemar_split16_conv(x0, workspace, bias, y, N, H, W, K, C, R, 1, H, W, OH, OW, mode, g_scratch, g_xcd_map, g_split16_variant,
-                               g_tl, nullptr, st);
+            nemar_split16_conv(x0, workspace, bias, y, N, H, W, K, C, R, 1, H, W, OH, OW, mode, call.scratch, g_xcd_map, g_split16_variant,
+                               g_tl, nullptr, call.src_max, call.src_planes, call.src_planes_kind, nullptr, nullptr, st);
             g_last_route = 2;
             NEMAR_CHECK_LAUNCH("conv2d_fwd (split-16)");
             return NEMAR_OK;
@@ -977,10 +965,11 @@ NEMAR_API size_t nemar_conv2d_bwd_data_workspace(int N, int C, int H, int W, int
     return sizeof(float) * dgrad_layout(N, C, H, W, K, R, S, stride, pad, pad_mode).total;
 }
 
-NEMAR_API int nemar_conv2d_bwd_data(const float* gy, const float* w, const float* bias, int act, float slope,
-                                    float* gx0, int C0, float* gx1, int C1, int N, int H, int W, int K, int OH, int OW,
-                                    int R, int S, int stride, int pad, int pad_mode, void* workspace, size_t ws_bytes,
-                                    int prepacked, void* stream) {
+// Honours call.scratch, .src_max, .src_planes, .gy_planes_out, .addend and .out_max; sets .gy_planes_written, .epilogue_fused, .addend_done
+static int conv2d_bwd_data(ConvCall& call, const float* gy, const float* w, const float* bias, int act, float slope,
+                           float* gx0, int C0, float* gx1, int C1, int N, int H, int W, int K, int OH, int OW,
+                           int R, int S, int stride, int pad, int pad_mode, void* workspace, size_t ws_bytes,
+                           int prepacked, void* stream) {
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(gy && w && workspace && (gx0 || gx1), "conv2d_bwd_data: null pointer");
     NEMAR_REQUIRE(C0 >= 0 && C1 >= 0 && C0 + C1 > 0 && (C1 == 0 || gx1), "conv2d_bwd_data: bad channel split");
@@ -1040,18 +1029,18 @@ NEMAR_API int nemar_conv2d_bwd_data(const float* gy, const float* w, const float
         const int mode = refl ? SPLIT16_DGRAD_REFLECT : SPLIT16_ZERO;
         if (g_split16 && C1 == 0 && gx0 && !bias && act == ACT_NONE && split16_worth_it(N, OH, OW, K, C, R, S) &&
             nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, mode, g_split16_variant) &&
-            g_scratch && g_scratch_bytes >= nemar_split16_scratch_total(N, H, W, C, K, H, W)) {
+            call.scratch && call.scratch_bytes >= nemar_split16_scratch_total(N, H, W, C, K, H, W)) {
             if (!prepacked) nemar_split16_pack(w, workspace, K, C, R, 1, g_split16_variant, st);
             void* dual = nullptr;      // the weight gradient of the same layer follows and takes its gy planes from this call's split pass
-            if (g_dual_gy && R == 3 && t_gy_planes_out && t_gy_planes_bytes >= nemar_split16_wgrad_g_bytes(N, H, W, K, R) &&
+            if (g_dual_gy && R == 3 && call.gy_planes_out && call.gy_planes_bytes >= nemar_split16_wgrad_g_bytes(N, H, W, K, R) &&
                 nemar_split16_wgrad_g_bytes(N, H, W, K, R) > 0 && nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad))
-                dual = t_gy_planes_out;
+                dual = call.gy_planes_out;
             // (whether the planes were written is the split pass's own decision: variant, producer planes, g_dual_gy — ask it)
-            nemar_split16_set_epilogue(t_addend, t_out_max);
-            t_gy_planes_written = nemar_split16_conv(gy, workspace, nullptr, gx0, N, H, W, C, K, R, R - 1 - pad, OH, OW, H, W, mode, g_scratch,
-                                                     g_xcd_map, g_split16_variant, g_tl, dual, st) ? 1 : 0;
-            t_fused_epilogue = nemar_split16_epilogue_done();
-            nemar_split16_set_epilogue(nullptr, nullptr);
+            const Split16Done done = nemar_split16_conv(gy, workspace, nullptr, gx0, N, H, W, C, K, R, R - 1 - pad, OH, OW, H, W, mode, call.scratch,
+                                                        g_xcd_map, g_split16_variant, g_tl, dual, call.src_max, call.src_planes,
+                                                        call.src_planes_kind, call.addend, call.out_max, st);
+            call.gy_planes_written = done.dual_written;
+            call.epilogue_fused = done.epilogue_fused;
             g_last_route = 2;
             NEMAR_CHECK_LAUNCH("conv2d_bwd_data (split-16)");
             return NEMAR_OK;
@@ -1084,8 +1073,8 @@ NEMAR_API int nemar_conv2d_bwd_data(const float* gy, const float* w, const float
             nemar_s16g_conv(q, pl, workspace, st);
             const long long total = (long long)N * C * H * W;
             hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, (const float*)padded16, gx0, H,
-                               W, pad, total, t_addend);
-            if (t_addend) t_addend_done = 1;
+                               W, pad, total, call.addend);
+            if (call.addend) call.addend_done = true;
             g_last_route = 3;
             NEMAR_CHECK_LAUNCH("conv2d_bwd_data (16-bit pipe on the padded domain + fold)");
             return NEMAR_OK;
@@ -1174,8 +1163,8 @@ NEMAR_API int nemar_conv2d_bwd_data(const float* gy, const float* w, const float
                 }
                 launch_igemm(p, st);
                 if (p.ksplit > 1 && fold) {                       // slabs of the padded domain -> sum + fold in one pass (gx1 == nullptr: checked above)
-                    nemar_sum_partials_fold(p.part, p.part_stride, p.ksplit, gx0, (long long)N * C, H, W, pad, t_addend, st);
-                    if (t_addend) t_addend_done = 1;
+                    nemar_sum_partials_fold(p.part, p.part_stride, p.ksplit, gx0, (long long)N * C, H, W, pad, call.addend, st);
+                    if (call.addend) call.addend_done = true;
                     folded = true;
                 }
                 else if (p.ksplit > 1 && gx1) nemar_sum_partials_two(p.part, p.part_stride, p.ksplit, gx0, gx1, N, C0, C1, H * W, st);
@@ -1211,10 +1200,10 @@ NEMAR_API int nemar_conv2d_bwd_data(const float* gy, const float* w, const float
         }
     if (fold && !folded) {
         const long long total = (long long)N * C * H * W;
-        const float* const add = (gx0 && !gx1) ? t_addend : nullptr;
+        const float* const add = (gx0 && !gx1) ? call.addend : nullptr;
         hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st,
                            (const float*)padded, gx0 ? gx0 : gx1, H, W, pad, total, add);
-        if (add) t_addend_done = 1;
+        if (add) call.addend_done = true;
     }
     g_last_route = 0;
     NEMAR_CHECK_LAUNCH("conv2d_bwd_data");
@@ -1301,9 +1290,10 @@ NEMAR_API size_t nemar_conv2d_bwd_weight_workspace(int N, int C, int H, int W, i
 
 // gw[K][C][R][S] += d loss / d w, and (gb != NULL) gb[K] += sum_pixels gy   (always accumulate: the caller
 // zero-fills once per optimizer step)
-NEMAR_API int nemar_conv2d_bwd_weight(const float* x0, int C0, const float* x1, int C1, const float* gy, float* gw,
-                                      float* gb, int N, int H, int W, int K, int OH, int OW, int R, int S, int stride,
-                                      int pad, int pad_mode, void* workspace, size_t ws_bytes, void* stream) {
+// Honours call.scratch, .src_max (x0), .src2_max (gy), .x_planes, .src2_planes and .bias_partials (the wide route); sets .bias_rode
+static int conv2d_bwd_weight(ConvCall& call, const float* x0, int C0, const float* x1, int C1, const float* gy, float* gw,
+                             float* gb, int N, int H, int W, int K, int OH, int OW, int R, int S, int stride,
+                             int pad, int pad_mode, void* workspace, size_t ws_bytes, void* stream) {
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(x0 && gy && gw, "conv2d_bwd_weight: null pointer");
     NEMAR_REQUIRE(C0 > 0 && C1 >= 0 && (C1 == 0 || x1), "conv2d_bwd_weight: bad channel split");
@@ -1354,22 +1344,20 @@ NEMAR_API int nemar_conv2d_bwd_weight(const float* x0, int C0, const float* x1, 
         nemar_s16g_wgrad_eligible(N, C0, C1, H, W, K, OH, OW, R, S, stride, pad, pad_mode);
     const bool split16_wg = g_split16 && g_split16_variant == 4 && part && C1 == 0 && split16_worth_it(N, OH, OW, K, C0, R, S) &&
         nemar_split16_wgrad_eligible(N, C0, H, W, K, R, S, stride, pad) &&
-        (R == 3 || pad_mode == BORDER_ZERO) && g_scratch && g_scratch_bytes >= nemar_split16_wgrad_scratch_bytes(N, C0, H, W, K, R);
+        (R == 3 || pad_mode == BORDER_ZERO) && call.scratch && call.scratch_bytes >= nemar_split16_wgrad_scratch_bytes(N, C0, H, W, K, R);
     if (s16g_wg && (g_s16g_wgrad_first || !split16_wg)) {
         nemar_s16g_wgrad(x0, C0, x1, C1, gy, gw, gb, N, H, W, K, OH, OW, R, stride, pad_mode, part, g_dbg, st);
         g_last_route = 3;
         NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (16-bit pipe, in-kernel split)");
         return NEMAR_OK;
     }
-    if (g_split16 && g_split16_variant == 4 && part && C1 == 0 && split16_worth_it(N, OH, OW, K, C0, R, S) &&
-        nemar_split16_wgrad_eligible(N, C0, H, W, K, R, S, stride, pad) &&
-        (R == 3 || pad_mode == BORDER_ZERO) && g_scratch && g_scratch_bytes >= nemar_split16_wgrad_scratch_bytes(N, C0, H, W, K, R)) {
+    if (split16_wg) {
         // wide 3x3 stride-1 layers: fp16 x 3 on the 16-bit matrix pipe (conv_split16_wgrad.hip); bias gradient as its own reduction
-        const bool bias_rides = gb && t_bias_partials;           // the producer's per-plane sums: reduced inside the slab-sum launch
-        if (bias_rides) { nemar_split16_wgrad_set_bias(t_bias_partials, gb); t_bias_rode = 1; }
-        nemar_split16_wgrad(x0, gy, gw, N, C0, H, W, K, R, pad_mode == BORDER_REFLECT ? 1 : 0, g_scratch, part, g_xcd_map,
-                            R == 3 ? t_src2_planes : nullptr, (R == 3 && pad_mode == BORDER_REFLECT) ? t_x_wplanes : nullptr, st);
-        if (gb && !bias_rides) {
+        call.bias_rode = gb && call.bias_partials;               // the producer's per-plane sums: reduced inside the slab-sum launch
+        nemar_split16_wgrad(x0, gy, gw, N, C0, H, W, K, R, pad_mode == BORDER_REFLECT ? 1 : 0, call.scratch, part, g_xcd_map,
+                            R == 3 ? call.src2_planes : nullptr, (R == 3 && pad_mode == BORDER_REFLECT) ? call.x_planes : nullptr,
+                            call.src_max, call.src2_max, call.bias_rode ? call.bias_partials : nullptr, gb, st);
+        if (gb && !call.bias_rode) {
             const int chunks = nemar_cdiv(OH * OW, BIAS_CHUNK);
             float* pb = part + (size_t)nemar_split16_wgrad_splits(N, C0, H, W, K, R) * K * J;
             hipLaunchKernelGGL(bias_grad_kernel, dim3(K, N, chunks), dim3(256), 0, st, gy, pb, N, K, OH * OW, BIAS_CHUNK);
@@ -1482,34 +1470,22 @@ NEMAR_API int nemar_tune(int key, int value) {
 }
 #endif  // NEMAR_AB
 
-// ---- the side inputs of the wide-layer route (scratch arena, per-sample max words, producer-written planes) travel WITH the call
-// (nemar_conv_extras): nothing is registered process-wide.  Inside the library they are thread-local for the duration of the call.
-namespace {
-struct ExtrasScope {
-    const void* t0 = nullptr;
-    const void* t1 = nullptr;
-    const void* tp = nullptr;
-    // planes_kind: the SPLIT16_* content extras.src_planes holds for this call (-1: the call takes no channel-blocked planes)
-    ExtrasScope(const nemar_conv_extras* ex, const void* src, const void* src2, int N, int C, int H, int W, int planes_kind) {
-        if (!ex) return;
-        if (ex->scratch && ex->scratch_bytes) { t_scratch = ex->scratch; t_scratch_bytes = ex->scratch_bytes; }
-        if (ex->src_max_words && ex->src_max_count > 0) { nemar_split16_set_hint(src, ex->src_max_words, ex->src_max_count); t0 = src; }
-        if (src2 && ex->src2_max_words && ex->src2_max_count > 0) { nemar_split16_set_hint(src2, ex->src2_max_words, ex->src2_max_count); t1 = src2; }
-        if (ex->src_planes && planes_kind >= 0) { nemar_split16_set_planes_hint(src, ex->src_planes, N, C, H, W, planes_kind); tp = src; }
-        t_gy_planes_out = ex->gy_planes_out; t_gy_planes_bytes = ex->gy_planes_bytes;
-        t_src2_planes = ex->src2_planes;
-        t_addend = ex->addend; t_out_max = ex->out_max_words;
+// Scratch bytes nemar_conv2d_fwd / nemar_conv2d_bwd_data want for this layer (0: the layer never uses the arena)
+NEMAR_API size_t nemar_conv2d_scratch(int N, int H, int W, int K, int C, int R, int S, int stride, int pad) {
+    if (N <= 0 || H <= 0 || W <= 0 || K <= 0 || C <= 0) return 0;
+    if (!g_split16 || !split16_worth_it(N, H + 2 * pad - R + 1, W + 2 * pad - S + 1, K, C, R, S)) return 0;
+    size_t b = 0;
+    if (nemar_split16_eligible(N, H, W, K, C, R, S, stride, pad, SPLIT16_ZERO, 4)) b = nemar_split16_scratch_total(N, H, W, K, C, H, W);
+    if (nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, SPLIT16_ZERO, 4)) {
+        const size_t d = nemar_split16_scratch_total(N, H, W, C, K, H, W);
+        if (d > b) b = d;
     }
-    ~ExtrasScope() {
-        t_scratch = nullptr; t_scratch_bytes = 0;
-        t_gy_planes_out = nullptr; t_gy_planes_bytes = 0; t_src2_planes = nullptr;
-        t_addend = nullptr; t_out_max = nullptr; t_x_wplanes = nullptr; t_bias_partials = nullptr;
-        if (t0) nemar_split16_set_hint(t0, nullptr, 0);
-        if (t1) nemar_split16_set_hint(t1, nullptr, 0);
-        if (tp) nemar_split16_set_planes_hint(tp, nullptr, 0, 0, 0, 0, 0);
+    if (nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad)) {
+        const size_t d = nemar_split16_wgrad_scratch_bytes(N, C, H, W, K, R);
+        if (d > b) b = d;
     }
-};
-}  // namespace
+    return b;
+}
 
 // bytes of the gy planes the data-gradient call of a layer can leave behind for its weight-gradient call (nemar_conv_extras.gy_planes_out /
 // .src2_planes); 0 = the layer's gradients do not both run on the wide route
@@ -1532,7 +1508,6 @@ NEMAR_API int nemar_conv2d_bwd_data_fusable(int N, int C, int H, int W, int K, i
 // 1 when nemar_conv2d_bwd_data_ex of this layer (one destination, no bias, no activation) adds nemar_conv_extras.addend to the data gradient:
 // the wide route's fused epilogue, or a stride-1 reflect layer whose data gradient ends with a fold pass (the general 16-bit-pipe kernel
 // on the padded domain + fold; the tiny maps' split launch + sum-and-fold) — the addend is one more term of that pass.
-NEMAR_API size_t nemar_conv2d_scratch(int N, int H, int W, int K, int C, int R, int S, int stride, int pad);
 NEMAR_API int nemar_conv2d_bwd_data_addend_ok(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return 0;
     if (nemar_conv2d_bwd_data_fusable(N, C, H, W, K, R, S, stride, pad, pad_mode)) return 1;
@@ -1545,31 +1520,62 @@ NEMAR_API int nemar_conv2d_bwd_data_addend_ok(int N, int C, int H, int W, int K,
 
 // 1 when the last nemar_conv2d_bwd_data_ex call on this thread filled its gy_planes_out buffer (the route it took supports it): only then
 // may the buffer be handed to nemar_conv2d_bwd_weight_ex as src2_planes
-NEMAR_API int nemar_last_gy_planes(void) { return t_gy_planes_written; }
+NEMAR_API int nemar_last_gy_planes(void) { return g_last_gy_planes; }
+
+// ---- the C-ABI entry points of the three operators.  The side inputs of the wide-layer route (scratch arena, per-sample max words,
+// producer-written planes) travel WITH the call (nemar_conv_extras): nothing is registered, per process or per thread.  Each _ex entry
+// copies the members its operator documents into the ConvCall the operator runs with; the plain entries run with an empty one.
+namespace {
+// what every operator takes: the arena and the source's max words
+ConvCall call_from(const nemar_conv_extras* ex) {
+    ConvCall call;
+    if (!ex) return call;
+    if (ex->scratch && ex->scratch_bytes) { call.scratch = ex->scratch; call.scratch_bytes = ex->scratch_bytes; }
+    if (ex->src_max_words && ex->src_max_count > 0) call.src_max = {(const unsigned*)ex->src_max_words, ex->src_max_count};
+    return call;
+}
+}  // namespace
+
+NEMAR_API int nemar_conv2d_fwd(const float* x0, int C0, const float* x1, int C1, const float* w, const float* bias,
+                               float* y, int N, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode,
+                               int act, float slope, void* workspace, size_t ws_bytes, int prepacked, void* stream) {
+    ConvCall call;
+    return conv2d_fwd(call, x0, C0, x1, C1, w, bias, y, N, H, W, K, R, S, stride, pad, pad_mode, act, slope, workspace, ws_bytes, prepacked, stream);
+}
 
 NEMAR_API int nemar_conv2d_fwd_ex(const float* x0, int C0, const float* x1, int C1, const float* w, const float* bias, float* y, int N,
                                   int H, int W, int K, int R, int S, int stride, int pad, int pad_mode, int act, float slope,
                                   void* workspace, size_t ws_bytes, int prepacked, void* stream, const nemar_conv_extras* extras) {
-    nemar_conv_extras e;
-    if (extras) { e = *extras; e.gy_planes_out = nullptr; e.gy_planes_bytes = 0; e.src2_planes = nullptr; e.addend = nullptr; e.out_max_words = nullptr; }
-    ExtrasScope scope(extras ? &e : nullptr, x0, nullptr, N, C0 + C1, H, W, SPLIT16_REFLECT);
-    return nemar_conv2d_fwd(x0, C0, x1, C1, w, bias, y, N, H, W, K, R, S, stride, pad, pad_mode, act, slope, workspace, ws_bytes, prepacked, stream);
+    ConvCall call = call_from(extras);
+    if (extras) { call.src_planes = extras->src_planes; call.src_planes_kind = SPLIT16_REFLECT; }      // (a forward producer's planes)
+    return conv2d_fwd(call, x0, C0, x1, C1, w, bias, y, N, H, W, K, R, S, stride, pad, pad_mode, act, slope, workspace, ws_bytes, prepacked, stream);
+}
+
+NEMAR_API int nemar_conv2d_bwd_data(const float* gy, const float* w, const float* bias, int act, float slope,
+                                    float* gx0, int C0, float* gx1, int C1, int N, int H, int W, int K, int OH, int OW,
+                                    int R, int S, int stride, int pad, int pad_mode, void* workspace, size_t ws_bytes,
+                                    int prepacked, void* stream) {
+    ConvCall call;
+    return conv2d_bwd_data(call, gy, w, bias, act, slope, gx0, C0, gx1, C1, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, workspace, ws_bytes,
+                           prepacked, stream);
 }
 
 NEMAR_API int nemar_conv2d_bwd_data_ex(const float* gy, const float* w, const float* bias, int act, float slope, float* gx0, int C0,
                                        float* gx1, int C1, int N, int H, int W, int K, int OH, int OW, int R, int S, int stride, int pad,
                                        int pad_mode, void* workspace, size_t ws_bytes, int prepacked, void* stream,
                                        const nemar_conv_extras* extras) {
-    nemar_conv_extras e;
-    if (extras) { e = *extras; e.src2_planes = nullptr; }
-    // (extras.src_planes: the data-gradient planes of gy nemar_instnorm_bwd_planes wrote, in the content of THIS layer's padding)
-    ExtrasScope scope(extras ? &e : nullptr, gy, nullptr, N, K, OH, OW, pad_mode == BORDER_REFLECT ? SPLIT16_DGRAD_REFLECT : SPLIT16_ZERO);
-    t_gy_planes_written = 0;
-    t_fused_epilogue = 0;
-    t_addend_done = 0;
-    const int rc = nemar_conv2d_bwd_data(gy, w, bias, act, slope, gx0, C0, gx1, C1, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, workspace,
-                                         ws_bytes, prepacked, stream);
-    if (rc == NEMAR_OK && extras && ((extras->addend && !t_fused_epilogue && !t_addend_done) || (extras->out_max_words && !t_fused_epilogue))) {
+    ConvCall call = call_from(extras);
+    if (extras) {
+        // (src_planes: the data-gradient planes of gy nemar_instnorm_bwd_planes wrote, in the content of THIS layer's padding)
+        call.src_planes = extras->src_planes;
+        call.src_planes_kind = pad_mode == BORDER_REFLECT ? SPLIT16_DGRAD_REFLECT : SPLIT16_ZERO;
+        call.gy_planes_out = extras->gy_planes_out; call.gy_planes_bytes = extras->gy_planes_bytes;
+        call.addend = extras->addend; call.out_max = extras->out_max_words;
+    }
+    const int rc = conv2d_bwd_data(call, gy, w, bias, act, slope, gx0, C0, gx1, C1, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, workspace,
+                                   ws_bytes, prepacked, stream);
+    g_last_gy_planes = call.gy_planes_written ? 1 : 0;
+    if (rc == NEMAR_OK && ((call.addend && !call.epilogue_fused && !call.addend_done) || (call.out_max && !call.epilogue_fused))) {
         nemar_set_error("conv2d_bwd_data_ex: this layer's route has no fused epilogue (addend / out_max_words): ask nemar_conv2d_bwd_data_fusable / "
                         "nemar_conv2d_bwd_data_addend_ok first");
         return NEMAR_EINVAL;
@@ -1577,18 +1583,26 @@ NEMAR_API int nemar_conv2d_bwd_data_ex(const float* gy, const float* w, const fl
     return rc;
 }
 
+NEMAR_API int nemar_conv2d_bwd_weight(const float* x0, int C0, const float* x1, int C1, const float* gy, float* gw,
+                                      float* gb, int N, int H, int W, int K, int OH, int OW, int R, int S, int stride,
+                                      int pad, int pad_mode, void* workspace, size_t ws_bytes, void* stream) {
+    ConvCall call;
+    return conv2d_bwd_weight(call, x0, C0, x1, C1, gy, gw, gb, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, workspace, ws_bytes, stream);
+}
+
 NEMAR_API int nemar_conv2d_bwd_weight_ex(const float* x0, int C0, const float* x1, int C1, const float* gy, float* gw, float* gb, int N,
                                          int H, int W, int K, int OH, int OW, int R, int S, int stride, int pad, int pad_mode,
                                          void* workspace, size_t ws_bytes, void* stream, const nemar_conv_extras* extras) {
-    nemar_conv_extras e;
-    if (extras) { e = *extras; e.gy_planes_out = nullptr; e.gy_planes_bytes = 0; e.addend = nullptr; e.out_max_words = nullptr; }
-    // (extras.src_planes: the weight gradient's X planes of x0 nemar_instnorm_fwd_planes wrote — pixel-major, not a channel-blocked hint)
-    ExtrasScope scope(extras ? &e : nullptr, x0, gy, N, C0 + C1, H, W, -1);
-    t_x_wplanes = extras ? extras->src_planes : nullptr;
-    t_bias_partials = extras ? extras->bias_partials : nullptr;
-    t_bias_rode = 0;
-    const int rc = nemar_conv2d_bwd_weight(x0, C0, x1, C1, gy, gw, gb, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, workspace, ws_bytes, stream);
-    if (rc == NEMAR_OK && extras && extras->bias_partials && gb && !t_bias_rode) {
+    ConvCall call = call_from(extras);
+    if (extras) {
+        if (extras->src2_max_words && extras->src2_max_count > 0) call.src2_max = {(const unsigned*)extras->src2_max_words, extras->src2_max_count};
+        // (src_planes: the weight gradient's X planes of x0 nemar_instnorm_fwd_planes wrote — pixel-major, not the channel-blocked kind)
+        call.x_planes = extras->src_planes;
+        call.src2_planes = extras->src2_planes;
+        call.bias_partials = extras->bias_partials;
+    }
+    const int rc = conv2d_bwd_weight(call, x0, C0, x1, C1, gy, gw, gb, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, workspace, ws_bytes, stream);
+    if (rc == NEMAR_OK && call.bias_partials && gb && !call.bias_rode) {
         nemar_set_error("conv2d_bwd_weight_ex: bias_partials are only taken on the wide route (nemar_conv2d_bwd_data_fusable); gb was reduced from gy");
         return NEMAR_EINVAL;
     }
@@ -1596,7 +1610,7 @@ NEMAR_API int nemar_conv2d_bwd_weight_ex(const float* x0, int C0, const float* x
 }
 
 // max |t| (finite elements) per sample of a tensor, for callers that feed the same tensor to several split-16 convolution calls
-// (forward + weight gradient take x, data + weight gradient take gy): computed once, registered with nemar_absmax_hint, it replaces
+// (forward + weight gradient take x, data + weight gradient take gy): computed once, passed as nemar_conv_extras.src_max_words, it replaces
 // the max pass inside each call.  nemar_absmax = one sample of n elements.
 NEMAR_API int nemar_absmax(const float* t, long long n, void* out_word, void* stream) {
     NEMAR_CLEAR_HIP_ERROR();
@@ -1625,23 +1639,6 @@ NEMAR_API int nemar_kernel_timer_read(double* total_ms, double* total_flop, int*
     NEMAR_REQUIRE(total_ms && total_flop && launches, "kernel_timer_read: null pointer");
     *launches = nemar_split16_timer_read(total_ms, total_flop);
     return NEMAR_OK;
-}
-
-// Scratch bytes nemar_conv2d_fwd / nemar_conv2d_bwd_data want for this layer (0: the layer never uses the arena)
-NEMAR_API size_t nemar_conv2d_scratch(int N, int H, int W, int K, int C, int R, int S, int stride, int pad) {
-    if (N <= 0 || H <= 0 || W <= 0 || K <= 0 || C <= 0) return 0;
-    if (!g_split16 || !split16_worth_it(N, H + 2 * pad - R + 1, W + 2 * pad - S + 1, K, C, R, S)) return 0;
-    size_t b = 0;
-    if (nemar_split16_eligible(N, H, W, K, C, R, S, stride, pad, SPLIT16_ZERO, 4)) b = nemar_split16_scratch_total(N, H, W, K, C, H, W);
-    if (nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, SPLIT16_ZERO, 4)) {
-        const size_t d = nemar_split16_scratch_total(N, H, W, C, K, H, W);
-        if (d > b) b = d;
-    }
-    if (nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad)) {
-        const size_t d = nemar_split16_wgrad_scratch_bytes(N, C, H, W, K, R);
-        if (d > b) b = d;
-    }
-    return b;
 }
 
 NEMAR_API size_t nemar_bias_grad_workspace(int N, int C, int HW) {

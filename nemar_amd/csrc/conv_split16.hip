@@ -741,70 +741,7 @@ unsigned* pack_max_word(void* packed, int M, int Cred, int KS) {
     return (unsigned*)((char*)packed + nemar_split16_pack_bytes(M, Cred, KS) - 64);
 }
 
-// nemar_absmax_hint: max |t| words the caller has already computed for tensors the next calls take as sources (count words: one per
-// sample of the tensor, or 1 = one for the whole tensor)
-thread_local const void* g_hint_tensor[4] = {nullptr, nullptr, nullptr, nullptr};      // (per calling thread, like the route note)
-thread_local const unsigned* g_hint_word[4] = {nullptr, nullptr, nullptr, nullptr};
-thread_local int g_hint_count[4] = {0, 0, 0, 0};
-// nemar_planes_hint: the fp16 x 3 planes of a source already exist (a producer wrote them: norm_planes.hip) — reflect 3x3 layout only
-// kind = the SPLIT16_* content the planes hold (SPLIT16_REFLECT: a forward producer's; SPLIT16_ZERO / SPLIT16_DGRAD_REFLECT: the
-// data-gradient planes nemar_instnorm_bwd_planes writes)
-struct PlanesHint { const void* tensor; const void* planes; int N, C, H, W, kind; };
-thread_local PlanesHint g_planes_hint[2] = {{nullptr, nullptr, 0, 0, 0, 0, 0}, {nullptr, nullptr, 0, 0, 0, 0, 0}};
 }  // namespace
-
-void nemar_split16_set_planes_hint(const void* tensor, const void* planes, int N, int C, int H, int W, int kind) {
-    int slot = -1;
-    for (int i = 0; i < 2; ++i)
-        if (g_planes_hint[i].tensor == tensor) slot = i;
-    if (!planes) {
-        if (slot >= 0) g_planes_hint[slot] = PlanesHint{nullptr, nullptr, 0, 0, 0, 0, 0};
-        return;
-    }
-    if (slot < 0) slot = g_planes_hint[0].tensor ? 1 : 0;
-    g_planes_hint[slot] = PlanesHint{tensor, planes, N, C, H, W, kind};
-}
-
-static const void* planes_hint_for(const void* tensor, int N, int C, int H, int W, int kind) {
-    for (int i = 0; i < 2; ++i) {
-        const PlanesHint& h = g_planes_hint[i];
-        if (h.tensor == tensor && tensor && h.N == N && h.C == C && h.H == H && h.W == W && h.kind == kind) return h.planes;
-    }
-    return nullptr;
-}
-
-// the epilogue side inputs of the next nemar_split16_conv call on this thread (conv.hip sets them from nemar_conv_extras, one call)
-thread_local const float* g_s16_addend = nullptr;
-thread_local unsigned* g_s16_maxw = nullptr;
-thread_local int g_s16_epilogue_done = 0;
-void nemar_split16_set_epilogue(const float* addend, void* max_words) { g_s16_addend = addend; g_s16_maxw = (unsigned*)max_words; g_s16_epilogue_done = 0; }
-int nemar_split16_epilogue_done() { return g_s16_epilogue_done; }
-
-const unsigned* nemar_split16_hint(const void* tensor, int* count) {
-    for (int i = 0; i < 4; ++i)
-        if (g_hint_tensor[i] == tensor && tensor) {
-            *count = g_hint_count[i];
-            return g_hint_word[i];
-        }
-    return nullptr;
-}
-
-void nemar_split16_set_hint(const void* tensor, const void* word, int count) {
-    int slot = -1;
-    for (int i = 0; i < 4; ++i)
-        if (g_hint_tensor[i] == tensor) slot = i;
-    if (!word) {
-        if (slot >= 0) { g_hint_tensor[slot] = nullptr; g_hint_word[slot] = nullptr; g_hint_count[slot] = 0; }
-        return;
-    }
-    if (slot < 0)
-        for (int i = 0; i < 4 && slot < 0; ++i)
-            if (!g_hint_tensor[i]) slot = i;
-    if (slot < 0) slot = 0;
-    g_hint_tensor[slot] = tensor;
-    g_hint_word[slot] = (const unsigned*)word;
-    g_hint_count[slot] = count;
-}
 
 // out: `samples` words, zero on entry
 void nemar_split16_absmax(const float* x, int samples, long long per, void* out, hipStream_t st) {
@@ -813,14 +750,10 @@ void nemar_split16_absmax(const float* x, int samples, long long per, void* out,
     hipLaunchKernelGGL(absmax_kernel, dim3(grid, samples), dim3(256), 0, st, x, per, (unsigned*)out);
 }
 
-// per-sample max |src| words for a split pass: the caller's hint (one word per sample, or one for all: *stride = 0), or computed
-// here into `own` (N words)
-const unsigned* nemar_split16_source_max(const float* src, int N, long long per, unsigned* own, int* stride, hipStream_t st) {
-    int count = 0;
-    const unsigned* h = nemar_split16_hint(src, &count);
-    if (h && (count == N || count == 1)) {
-        *stride = count == N && N > 1 ? 1 : 0;
-        return h;
+const unsigned* nemar_split16_source_max(const float* src, int N, long long per, MaxWords hint, unsigned* own, int* stride, hipStream_t st) {
+    if (hint.words && (hint.count == N || hint.count == 1)) {
+        *stride = hint.count == N && N > 1 ? 1 : 0;
+        return hint.words;
     }
     (void)hipMemsetAsync(own, 0, sizeof(unsigned) * N, st);
     nemar_split16_absmax(src, N, per, own, st);
@@ -903,22 +836,20 @@ NEMAR_SWITCH(int, g_split16_ring3, 0);         // nemar_tune(32, 1): 3-slot weig
                                  // (287.6 vs 292.3 us per call, bench 37.5 vs 37.2-37.5 ms) — the kernel needs 332 VGPRs (two fragment sets), so a
                                  // SIMD still holds ONE wave and the second workgroup never becomes resident; kept for the experiment only
 
-bool nemar_split16_conv(const float* src, const void* packed, const float* bias, float* dst, int N, int H, int W, int M, int Cred,
-                         int KS, int src_pad, int Hs, int Ws_src, int OH, int OW, int mode, void* scratch, int xcd_map, int variant,
-                         long long* tl, void* dual_g_out, hipStream_t st) {
+Split16Done nemar_split16_conv(const float* src, const void* packed, const float* bias, float* dst, int N, int H, int W, int M, int Cred,
+                               int KS, int src_pad, int Hs, int Ws_src, int OH, int OW, int mode, void* scratch, int xcd_map, int variant,
+                               long long* tl, void* dual_g_out, MaxWords src_max, const void* ready_planes, int ready_kind,
+                               const float* addend, void* out_max, hipStream_t st) {
     bool dual_written = false;
     const long long total = (long long)N * (Cred / 8) * (H + 4) * (W + 4);
     unsigned* const xmw = scratch_max_word(scratch, N, Cred, H, W);
     const unsigned* xmax = xmw;
     int xstride = 0;
-    const void* ready = nullptr;          // planes a producer already wrote (with the max-word hint they were scaled by)
-    if (variant == 4 && KS == 3 && src_pad == 1 && Hs == H && Ws_src == W) {
-        int count = 0;
-        ready = planes_hint_for(src, N, Cred, H, W, mode);
-        if (ready && !(nemar_split16_hint(src, &count) && count == N)) ready = nullptr;
-    }
+    // planes a producer already wrote, scaled by the per-sample words that come with them: [N, Cred, H, W] in this call's content
+    const void* const ready = (variant == 4 && KS == 3 && src_pad == 1 && Hs == H && Ws_src == W && ready_kind == mode &&
+                               src_max.words && src_max.count == N) ? ready_planes : nullptr;
     if (variant == 4) {
-        xmax = nemar_split16_source_max(src, N, (long long)Cred * Hs * Ws_src, xmw, &xstride, st);
+        xmax = nemar_split16_source_max(src, N, (long long)Cred * Hs * Ws_src, src_max, xmw, &xstride, st);
         if (!ready && dual_g_out && KS == 3 && src_pad == 1 && Hs == H && Ws_src == W && Cred % 64 == 0 &&
             (mode == SPLIT16_DGRAD_REFLECT || mode == SPLIT16_ZERO))
             // data gradient of a 3x3 layer whose weight gradient follows: both operand layouts of gy from one read (conv_split16_wgrad.hip)
@@ -960,11 +891,10 @@ bool nemar_split16_conv(const float* src, const void* packed, const float* bias,
     p.ksplit = nemar_split16_ksplit(N, H, W, M, Cred);
     p.slab_stride = (long long)N * M * OH * OW;
     // fused epilogue (skip-gradient add, per-sample max of the result): only where a tile's whole reduction runs in one workgroup
-    const bool fuse = p.ksplit == 1 && variant == 4 && KS == 3 && !bias && (g_s16_addend || g_s16_maxw);
-    p.addend = fuse ? g_s16_addend : nullptr;
-    p.maxw = fuse ? g_s16_maxw : nullptr;
+    const bool fuse = p.ksplit == 1 && variant == 4 && KS == 3 && !bias && (addend || out_max);
+    p.addend = fuse ? addend : nullptr;
+    p.maxw = fuse ? (unsigned*)out_max : nullptr;
     p.maxw_lazy = (p.maxw && nemar_max_words_lazy() && p.tiles_per_img * p.mblks <= 0xFFFF) ? 1 : 0;
-    g_s16_epilogue_done = fuse ? 1 : 0;
     float* const final_dst = dst;
     if (p.ksplit > 1) p.dst = (float*)((char*)scratch + nemar_split16_scratch_bytes(N, Cred, H, W));       // slabs behind the planes
     const int grid = tiles * p.ksplit;
@@ -1010,7 +940,7 @@ bool nemar_split16_conv(const float* src, const void* packed, const float* bias,
             else S16_GO(3, 2, 3, 4))
         if (p.ksplit > 1) nemar_sum_partials(p.dst, p.slab_stride, p.ksplit, final_dst, p.slab_stride, false, st);
         if (p.maxw && !p.maxw_lazy) max_words_finalize(p.maxw, N, p.tiles_per_img * p.mblks, st);
-        return dual_written;
+        return {dual_written, fuse};
     }
 #ifdef NEMAR_AB      // nemar_tune(21, 3): bf16 x 6 products
     if (variant == 3) {
@@ -1022,11 +952,11 @@ bool nemar_split16_conv(const float* src, const void* packed, const float* bias,
         } else if (nbw <= 2) S16_GO(2, 3, 3, 4)
         else S16_GO(3, 3, 3, 4)
         if (p.ksplit > 1) nemar_sum_partials(p.dst, p.slab_stride, p.ksplit, final_dst, p.slab_stride, false, st);
-        return dual_written;
+        return {dual_written, fuse};
     }
 #endif
 #undef S16_GO
 #undef S16_GO_
     (void)region;
-    return dual_written;
+    return {dual_written, fuse};
 }

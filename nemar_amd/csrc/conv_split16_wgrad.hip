@@ -510,12 +510,9 @@ void nemar_split16_dual_split(const float* gy, void* dplanes, void* gplanes, int
 #undef WG_DUAL
 }
 
-static thread_local const float* t_bias_partials = nullptr;
-static thread_local float* t_bias_dst = nullptr;
-void nemar_split16_wgrad_set_bias(const float* bias_partials, float* gb) { t_bias_partials = bias_partials; t_bias_dst = gb; }
-
 void nemar_split16_wgrad(const float* x, const float* gy, float* gw, int N, int C, int H, int W, int K, int KS, int reflect,
-                         void* scratch, float* part, int xcd_map, const void* g_planes, const void* x_planes, hipStream_t st) {
+                         void* scratch, float* part, int xcd_map, const void* g_planes, const void* x_planes, MaxWords x_max,
+                         MaxWords gy_max, const float* bias_partials, float* gb, hipStream_t st) {
     const int CPR = (W + 2 + 7) / 8, KBLK = K / 64, CBLK = C / 64;
     const int OHg = H + 3 - KS, OWg = W + 3 - KS, Hg = g_rows(H, KS), Hx = Hg + KS - 1;
     const long long gtotal = (long long)N * K * Hg * CPR, xtotal = (long long)N * C * Hx * CPR;      // words per plane block
@@ -526,8 +523,8 @@ void nemar_split16_wgrad(const float* x, const float* gy, float* gw, int N, int 
     u32x4* const X = have_x ? (u32x4*)const_cast<void*>(x_planes) : (u32x4*)scratch + 2 * (oneg ? 1 : KS) * gtotal;
     unsigned* const mw = (unsigned*)((char*)scratch + nemar_split16_wgrad_scratch_bytes(N, C, H, W, K, KS) - 2048);    // 2 x 256 words
     int gstride = 0, xstride = 0;
-    const unsigned* const gmax = nemar_split16_source_max(gy, N, (long long)K * OHg * OWg, mw, &gstride, st);
-    const unsigned* const xmax = nemar_split16_source_max(x, N, (long long)C * H * W, mw + 256, &xstride, st);
+    const unsigned* const gmax = nemar_split16_source_max(gy, N, (long long)K * OHg * OWg, gy_max, mw, &gstride, st);
+    const unsigned* const xmax = nemar_split16_source_max(x, N, (long long)C * H * W, x_max, mw + 256, &xstride, st);
 #define WG_SPLIT(TW_)                                                                                                              \
     if (have_g) {                                                                                                                  \
     } else if (oneg)                                                                                                               \
@@ -564,6 +561,6 @@ void nemar_split16_wgrad(const float* x, const float* gy, float* gw, int N, int 
     else wg_launch<4, false>(grid, p, st);
 #endif
     // (+ the bias gradient from the backward producer's per-plane sums, where the caller handed them over: one launch for both reductions)
-    nemar_sum_partials_pair(part, (long long)K * C * KS * KS, splits, gw, (long long)K * C * KS * KS, t_bias_partials, K, N, t_bias_dst, K, true, st);
-    t_bias_partials = nullptr; t_bias_dst = nullptr;
+    nemar_sum_partials_pair(part, (long long)K * C * KS * KS, splits, gw, (long long)K * C * KS * KS, bias_partials, K, N,
+                            bias_partials ? gb : nullptr, K, true, st);
 }

@@ -12,7 +12,7 @@
 // itself.  And InstanceNorm has a bound: |xhat| <= sqrt(HW - 1) for every element of a plane (Samuelson), so
 //     B = sqrt(HW) [x 1/(1-p) under dropout]  (+ max |skip| of the sample, a word the previous producer published)
 // is known before the first element is written.  The word pair (bound for the scale, actual maximum for the next bound) travels with
-// the tensor; the consuming convolution takes the planes through nemar_planes_hint and skips its absmax + split passes.
+// the tensor; the consuming convolution takes the planes as nemar_conv_extras.src_planes and skips its absmax + split passes.
 //
 // One workgroup = one (sample, 8-channel group): 1024 threads x (4 consecutive pixels x 8 channels) — a thread owns whole 16-byte plane
 // words, the plane is read once (float4 per channel), statistics are the exact two-pass form of norm.hip from registers.

@@ -403,7 +403,7 @@ class _lazy_max:
 
 
 def _absmax_word_compute(t):
-    """max |t| PER SAMPLE as the N-word tensor nemar_absmax_hint takes (the fp16 split of the wide 3x3 layers scales every sample by
+    """max |t| PER SAMPLE as the N-word tensor nemar_conv_extras.src_max_words takes (the fp16 split of the wide 3x3 layers scales every sample by
     a power of two derived from its own maximum).  Computed once per tensor and shared by the calls that take it as a source.
     Words come out of a pre-zeroed pool: one fill launch per 4096 of them instead of one per tensor."""
     n = int(t.shape[0])

@@ -25,9 +25,6 @@ def ws(nbytes, device):
     return guarded('ws', (device, ops._lane[0]), max(int(nbytes) // 4 + 64, 1 << 20), device)
 
 
-orig_scratch = ops._conv_scratch
-
-
 def scratch(N, H, W, K, C, R, S, stride, pad, device):
     need = ops.L.conv2d_scratch(N, H, W, K, C, R, S, stride, pad)
     if not need:
