@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 605 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 606 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -445,6 +445,39 @@ int nemar_registration_error(const float* pred, int grid_mode, const float* g, f
 #define NEMAR_SAMPLE_NEAREST 1
 int nemar_warp_resampled_fwd(const float* in, const float* pred, int grid_mode, int sample_mode, float* out,
                              int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* stream);
+
+/* Scoring a registration of real data (csrc/score.hip; not in the reference, which has no evaluation code): segmentation overlap and
+ * annotated-point distances, both read off the transformation exactly as nemar_warp_resampled_fwd applies it.  pred, grid_mode, hf and
+ * wf are what that entry point takes (NEMAR_GRID_UNET offsets [N,2,hf,wf], resized in registers; NEMAR_GRID_AFFINE dtheta [N,6], hf and
+ * wf ignored; NEMAR_GRID_EXPLICIT is NEMAR_EINVAL).
+ *
+ * nemar_label_overlap: the nearest-sampled warp of a label map and its per-class counts against the fixed map, in one pass.
+ * labels_moving [N,Hs,Ws] (modality A's map, any size), labels_fixed [N,Ho,Wo].  For output pixel x, m(x) is the value
+ * nemar_warp_resampled_fwd(..., NEMAR_SAMPLE_NEAREST) would write there (position rounded half-to-even, 0 where the texel is outside the
+ * source) — the same code computes it; the warped map is never written to memory — and f(x) = labels_fixed(x).
+ * A value v belongs to class k iff v == (float)k for an integer 0 <= k < K; any other value (negative, >= K, fractional, NaN, Inf)
+ * belongs to no class on that side and is not counted.  Zero padding is the value 0: pixels warped from outside the source count as
+ * class 0 (the background id by the usual convention; score foreground classes only if that matters).
+ * counts [N,K,3] uint32 is OVERWRITTEN (cleared on `stream` by the entry point; no workspace): per sample and class
+ *   [0] inter = #{x : m(x) == k and f(x) == k}    [1] moving = #{x : m(x) == k}    [2] fixed = #{x : f(x) == k}
+ * Dice_k = 2 inter / (moving + fixed) is the caller's arithmetic.  The score BEFORE registration is the same call with an identity
+ * prediction (NEMAR_GRID_AFFINE, dtheta = 0), which also brings maps of different sizes together.
+ * The counts are integers, added with integer atomics: the result does not depend on the order of the additions and is bitwise
+ * repeatable — no fixed-order merge is needed (nemar_registration_error's float sums need one).
+ * NEMAR_EINVAL, nothing launched: K outside 1 .. 1024, Ho*Wo or Hs*Ws >= 2^31, a non-positive size, N > 65535, hf or wf < 1 with
+ * NEMAR_GRID_UNET, a null pointer or one that is not 4-byte aligned (odd widths and views off the 16-byte grid take the normal route). */
+int nemar_label_overlap(const float* labels_moving, const float* labels_fixed, const float* pred, int grid_mode, unsigned* counts,
+                        int N, int K, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* stream);
+/* nemar_map_points: the transformation at annotated points.  pts [N,P,2] = (x, y) in pixels of the fixed image at size (Ho,Wo), fractional
+ * values and points beyond the border allowed; out [N,P,2] = S(p), the position in pixels of the (Hs,Ws) source that the warp samples for
+ * p: the continuous extension of nemar_warp_resampled_fwd's grid, ((g + 1) * size_s - 1) / 2 of
+ *   NEMAR_GRID_UNET    g = -1 + 2p/(size-1) (linspace(-1,1,size) at integer p) + the align_corners=False bilinear resize of pred evaluated
+ *                      at p: source coordinate (p + 0.5) * hf/Ho - 0.5 clamped to [0, hf-1], the taps of nemar_bilinear_fwd; with
+ *                      (hf,wf) == (Ho,Wo) that is the bilinear interpolation of pred itself;
+ *   NEMAR_GRID_AFFINE  g = theta applied to the base coordinate (2p + 1)/size - 1 (affine_grid, align_corners=False).
+ * A NaN coordinate (a missing annotation) gives a NaN pair.  One lane per point, plain fp32. */
+int nemar_map_points(const float* pts, const float* pred, int grid_mode, float* out, int N, int P, int Hs, int Ws, int hf, int wf,
+                     int Ho, int Wo, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

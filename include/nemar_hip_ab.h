@@ -53,7 +53,9 @@ extern "C" {
  *   43 stride-1 reflect data gradients of tiny maps on the exact-fp32 kernels: one split launch over the padded domain + a sum-and-fold pass
  *      (1, default) / interior + border-ring launches with their sums and a gather (0)
  *   44 nemar_warp_resampled_fwd: 4 consecutive pixels per lane and 16-byte stores where Wo % 4 == 0 and out is 16-byte aligned (1) / one pixel
- *      per lane everywhere (0, default: the 16-byte form takes 27 - 37 % longer, profiles/register_fullres.txt) */
+ *      per lane everywhere (0, default: the 16-byte form takes 27 - 37 % longer, profiles/register_fullres.txt)
+ *   45 nemar_label_overlap: every lane adds to the workgroup's LDS histogram for itself (1) / the lanes that share the wave's first key are
+ *      added once, by a ballot (0, default; tools/profiles/label_overlap.txt) */
 int nemar_tune(int key, int value);
 int nemar_tune_ptr(void* timeline_buffer);   /* device buffer for per-stage cycle stamps (tools/timeline_*.py), NULL = off */
 /* grad_input variant for A/B measurements: 0 (default) = gather + fixed point (needs the workspace), 1 = fp32 atomics through an

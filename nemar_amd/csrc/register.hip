@@ -16,72 +16,14 @@
 // tools/microbench_register.py times the two side by side and profiles/register_fullres.txt holds the result, 16-byte stores take 27 % to
 // 37 % longer, as in warp.hip's forward kernel (profiles/r4_gs_fwd_vec.txt).  No pointer needs more than 4-byte alignment.
 //
-// Arithmetic is shared, not restated: grid and position from warp_grid.h, the resize taps and their sum from resize_taps.h, the
+// Arithmetic is shared, not restated: grid and position from warp_grid.h, the resize taps and their sum from resize_taps.h, the tile's
+// field patch and the texels a pixel reads from resampled_grid.h (shared with score.hip, which counts what this kernel would write), the
 // four-corner blend in the expression order of warp.hip's grid_sample_fwd_kernel.  With -ffp-contract=off the bilinear result equals
 // the composed path's bit for bit (tests/register_cases.py).
 #include "common.h"
-#include "resize_taps.h"
-#include "warp_grid.h"
+#include "resampled_grid.h"
 
 namespace {
-
-constexpr int SAMPLE_BILINEAR = 0;  // F.grid_sample(mode='bilinear')
-constexpr int SAMPLE_NEAREST = 1;   // F.grid_sample(mode='nearest'): round-half-to-even of the unnormalised position
-
-constexpr int RT_W = 64, RT_H = 16, RT_THREADS = 256;
-constexpr int RT_PW = RT_W + 2, RT_PH = RT_H + 2;      // the coarse patch of a tile when the field is not being down-sampled
-
-// the pixel's two interpolated field values from `f` (channel 0 at f, channel 1 at f + cstep; rows `pitch` apart; the taps' indices
-// relative to (oy, ox)) — called once with the LDS patch and once with the global field, so that each call keeps its address space
-__device__ __forceinline__ RegSrc field_at(const float* f, int pitch, int cstep, int oy, int ox, const Tap1D& th, const Tap1D& tw) {
-    const int r0 = (th.i0 - oy) * pitch, r1 = (th.i1 - oy) * pitch, c0 = tw.i0 - ox, c1 = tw.i1 - ox;
-    const float* g = f + cstep;
-    return RegSrc{resize_blend(f[r0 + c0], f[r0 + c1], f[r1 + c0], f[r1 + c1], tw, th),
-                  resize_blend(g[r0 + c0], g[r0 + c1], g[r1 + c0], g[r1 + c1], tw, th)};
-}
-
-// where one output pixel reads the source: up to four texel offsets (clamped into the image, so that the loads are unconditional and the
-// zeros of the padding are selected afterwards, as grid_sample_fwd_kernel does), their weights, bit k of `ok` = texel k is inside
-struct Taps {
-    int o00, o01, o10, o11;
-    float wnw, wne, wsw, wse;
-    unsigned ok;
-};
-template <int SAMPLE>
-__device__ __forceinline__ Taps taps_at(float gx, float gy, int Ws, int Hs) {
-    Taps t;
-    if (SAMPLE == SAMPLE_NEAREST) {
-        float ix, iy;
-        sample_position(gx, gy, Ws, Hs, ix, iy);
-        // round half to even (v_rndne_f32), clamped before the int conversion as locate() does
-        const int xn = (int)fminf(fmaxf(rintf(ix), -2.f), (float)Ws + 1.f);
-        const int yn = (int)fminf(fmaxf(rintf(iy), -2.f), (float)Hs + 1.f);
-        t.ok = ((unsigned)xn < (unsigned)Ws && (unsigned)yn < (unsigned)Hs) ? 1u : 0u;
-        t.o00 = t.o01 = t.o10 = t.o11 = min(max(yn, 0), Hs - 1) * Ws + min(max(xn, 0), Ws - 1);
-        t.wnw = t.wne = t.wsw = t.wse = 0.f;
-    } else {
-        const Sample s = locate(gx, gy, Ws, Hs);
-        const float ex = 1.f - s.tx, ey = 1.f - s.ty;
-        t.wnw = ex * ey; t.wne = s.tx * ey; t.wsw = ex * s.ty; t.wse = s.tx * s.ty;
-        const bool vx0 = (unsigned)s.x0 < (unsigned)Ws, vx1 = (unsigned)(s.x0 + 1) < (unsigned)Ws;
-        const bool vy0 = (unsigned)s.y0 < (unsigned)Hs, vy1 = (unsigned)(s.y0 + 1) < (unsigned)Hs;
-        t.ok = (vx0 && vy0 ? 1u : 0u) | (vx1 && vy0 ? 2u : 0u) | (vx0 && vy1 ? 4u : 0u) | (vx1 && vy1 ? 8u : 0u);
-        const int xa = min(max(s.x0, 0), Ws - 1), xb = min(max(s.x0 + 1, 0), Ws - 1);
-        const int ya = min(max(s.y0, 0), Hs - 1), yb = min(max(s.y0 + 1, 0), Hs - 1);
-        t.o00 = ya * Ws + xa; t.o01 = ya * Ws + xb; t.o10 = yb * Ws + xa; t.o11 = yb * Ws + xb;
-    }
-    return t;
-}
-// the pixel's value in plane p — the four-corner blend in grid_sample_fwd_kernel's expression order
-template <int SAMPLE>
-__device__ __forceinline__ float sample_at(const float* __restrict__ p, const Taps& t) {
-    if (SAMPLE == SAMPLE_NEAREST) {
-        const float r = p[t.o00];
-        return (t.ok & 1u) ? r : 0.f;
-    }
-    const float a = p[t.o00], b = p[t.o01], cc = p[t.o10], d = p[t.o11];
-    return ((t.ok & 1u) ? a : 0.f) * t.wnw + ((t.ok & 2u) ? b : 0.f) * t.wne + ((t.ok & 4u) ? cc : 0.f) * t.wsw + ((t.ok & 8u) ? d : 0.f) * t.wse;
-}
 
 // VEC: pixels of one row a lane owns per run — 1 (the product: four runs, in four rows of the tile) or 4 (measurement build: one run)
 template <int MODE, int SAMPLE, int VEC, bool RESAMPLE>
@@ -101,23 +43,9 @@ __global__ __launch_bounds__(RT_THREADS) void warp_resampled_kernel(const float*
     float* outN = out + (size_t)n * C * oplane;
     const float* fN = MODE == GRID_UNET ? pred + (size_t)n * 2 * (RESAMPLE ? (size_t)fplane : oplane) : nullptr;
 
-    // ---- the coarse-field texels this tile's pixels tap (tap1d is monotone in the pixel index: the first and the last pixel bound them) ----
-    int px0 = 0, py0 = 0;
-    bool staged = false;
+    FieldPatch fp{0, 0, false};
     if (RESAMPLE) {
-        const Tap1D ta = tap1d(x0, wf, sw), tb = tap1d(min(x0 + RT_W, Wo) - 1, wf, sw);
-        const Tap1D tc = tap1d(y0, hf, sh), td = tap1d(min(y0 + RT_H, Ho) - 1, hf, sh);
-        const int pw = tb.i1 - ta.i0 + 1, ph = td.i1 - tc.i0 + 1;
-        px0 = ta.i0;
-        py0 = tc.i0;
-        staged = pw <= RT_PW && ph <= RT_PH;             // (the same in every lane of the workgroup)
-        if (staged) {
-            for (int e = tid; e < 2 * ph * RT_PW; e += RT_THREADS) {
-                const int cr = e / RT_PW, rx = e - cr * RT_PW;      // cr: channel-major row of the patch
-                const int c = cr >= ph ? 1 : 0, ry = cr - c * ph;
-                if (rx < pw) patch[(c * RT_PH + ry) * RT_PW + rx] = fN[(size_t)c * fplane + (size_t)(py0 + ry) * wf + px0 + rx];
-            }
-        }
+        fp = stage_field(patch, fN, fplane, x0, y0, hf, wf, Ho, Wo, sh, sw, tid);
         __syncthreads();
     }
 
@@ -130,18 +58,8 @@ __global__ __launch_bounds__(RT_THREADS) void warp_resampled_kernel(const float*
 #pragma unroll
         for (int v = 0; v < VEC; ++v) {
             const int w = w0 + v;
-            RegSrc src{0.f, 0.f};                          // the pixel's two grid_src values
-            if (MODE == GRID_UNET) {
-                if (RESAMPLE) {
-                    const Tap1D ty = tap1d(h, hf, sh), tx = tap1d(w, wf, sw);
-                    src = staged ? field_at(patch, RT_PW, RT_PH * RT_PW, py0, px0, ty, tx) : field_at(fN, wf, fplane, 0, 0, ty, tx);
-                } else {
-                    const size_t o = (size_t)h * Wo + w;
-                    src = RegSrc{fN[o], fN[oplane + o]};
-                }
-            }
             float gx, gy;
-            grid_coord<MODE>(src, h, w, Ho, Wo, th, gx, gy);
+            resampled_coord<MODE, RESAMPLE>(patch, fp, fN, fplane, oplane, h, w, hf, wf, Ho, Wo, sh, sw, th, gx, gy);
             t[v] = taps_at<SAMPLE>(gx, gy, Ws, Hs);
         }
         float* q = outN + (size_t)h * Wo + w0;

@@ -11,14 +11,21 @@ constexpr int GRID_UNET = 1;      // offsets [N,2,Ho,Wo] planar; + linspace(-1,1
 constexpr int GRID_AFFINE = 2;    // dtheta [N,6]; theta = dtheta + [1,0,0,0,1,0]; affine_grid(align_corners=False)
 
 // torch.linspace(-1, 1, n)[i] in fp32: fused multiply-add from the nearer end (ATen RangeFactories
-// symmetric form; bit-exact against torch CPU, see tests/test_oracle_torch.py)
+// symmetric form; bit-exact against torch CPU, see tests/test_oracle_torch.py).  linspace_at is its continuous extension
+// -1 + 2p/(n-1) (score.hip: annotated points between pixels), the same expression — at an integer p the same bits
+__device__ __forceinline__ float linspace_at(float p, int n) {
+    if (n <= 1) return -1.f;
+    const float step = 2.f / (float)(n - 1);
+    return (2.f * p < (float)(n - 1)) ? fmaf(step, p, -1.f) : fmaf(-step, (float)(n - 1) - p, 1.f);
+}
 __device__ __forceinline__ float linspace_m1_p1(int i, int n) {
     if (n <= 1) return -1.f;
     const float step = 2.f / (float)(n - 1);
     return (i < n / 2) ? fmaf(step, (float)i, -1.f) : fmaf(-step, (float)(n - 1 - i), 1.f);
 }
-// affine_grid base coordinate, align_corners=False: (2i+1)/n - 1
-__device__ __forceinline__ float affine_base(int i, int n) { return (2.f * (float)i + 1.f) / (float)n - 1.f; }
+// affine_grid base coordinate, align_corners=False: (2i+1)/n - 1 (affine_base_at: at a continuous coordinate)
+__device__ __forceinline__ float affine_base_at(float p, int n) { return (2.f * p + 1.f) / (float)n - 1.f; }
+__device__ __forceinline__ float affine_base(int i, int n) { return affine_base_at((float)i, n); }
 
 // theta = dtheta + identity of sample n (reference models/stn/affine_stn.py:96,122)
 __device__ __forceinline__ void affine_theta(const float* gsrc, int n, float* th) {

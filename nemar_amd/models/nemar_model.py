@@ -202,7 +202,8 @@ class NEMARModel(BaseModel):
         cols[2] = rows[:, 2].max()
         return registration_summary(cols.tolist(), self.gt_field.size(0) * self.gt_field.size(2) * self.gt_field.size(3))
 
-    def register(self, full_A, full_B=None, labels_A=None, translate=True):
+    def register(self, full_A, full_B=None, labels_A=None, translate=True, labels_B=None, landmarks_A=None, landmarks_B=None,
+                 num_classes=None):
         """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the
         network's resolution) predicted: the sampling grid is in normalised coordinates, so the prediction holds at every size, and the
         warp kernel resizes a dense field on the fly (ops.warp_resampled).  full_A [N,C,H,W] is modality A of the same N pairs at any
@@ -212,7 +213,14 @@ class NEMARModel(BaseModel):
         netT can run at full_A's size — the key is absent otherwise, nothing is resized; 'registered_labels_A' (labels_A
         [N,*,H',W'] warped with nearest sampling: class ids are copied, never blended) when labels_A is given; 'offsets', the
         network-resolution prediction itself (offsets [N,2,h,w] or dtheta [N,6]).  full_B is accepted for symmetry with set_input and is
-        not read: the prediction is made from the network-resolution pair."""
+        not read: the prediction is made from the network-resolution pair.
+        Scores, where there is something to score against (ops.label_overlap / ops.map_points; no further keys and no further launches
+        otherwise): with labels_A and labels_B ([N,H,W] or [N,1,H,W], at the fixed image's size) 'overlap' and 'overlap_before', int32
+        [N,K,3] per-class counts (inter, moving, fixed — Dice = 2 inter / (moving + fixed)) of the warped label map and of labels_A
+        merely resampled to that size, K = num_classes or 1 + the largest id of the two maps (one host synchronisation); with
+        landmarks_A and landmarks_B ([N,P,2] (x, y) in pixels of full_A and of the fixed image, which is full_B's size, or full_A's
+        without full_B; NaN = missing) 'tre_px' and 'tre_before_px' [N,P]: |S(lm_B) - lm_A| with the prediction's S and with the
+        identity's, NaN where either point is missing."""
         pred = self.netR.last_prediction()
         if pred is None:
             raise RuntimeError('register: no forward pass yet')
@@ -226,6 +234,25 @@ class NEMARModel(BaseModel):
             if labels_A is not None:
                 labels_A = labels_A.to(self.device, dtype=torch.float32).contiguous()
                 out['registered_labels_A'] = self.netR.apply(pred, [labels_A], sample='nearest')[0]
+            score_labels = labels_A is not None and labels_B is not None
+            score_points = landmarks_A is not None and landmarks_B is not None
+            if score_labels or score_points:        # "before registration": the identity transformation, which also bridges two sizes
+                identity = (torch.zeros((pred[0].size(0), 6), dtype=torch.float32, device=self.device), ops.GRID_AFFINE)
+            if score_labels:
+                labels_B = labels_B.to(self.device, dtype=torch.float32).contiguous()
+                if num_classes is None:
+                    num_classes = int(torch.maximum(labels_A.max(), labels_B.max()).item()) + 1
+                out['overlap'] = ops.label_overlap(pred[0], pred[1], labels_A, labels_B, num_classes)
+                out['overlap_before'] = ops.label_overlap(identity[0], identity[1], labels_A, labels_B, num_classes)
+            if score_points:
+                lm_A = landmarks_A.to(self.device, dtype=torch.float32).contiguous()
+                lm_B = landmarks_B.to(self.device, dtype=torch.float32).contiguous()
+                if lm_A.shape != lm_B.shape:
+                    raise ValueError('register: landmarks_A %s and landmarks_B %s are no point pairs' % (tuple(lm_A.shape), tuple(lm_B.shape)))
+                src_hw = tuple(full_A.shape[2:])
+                out_hw = src_hw if full_B is None else tuple(full_B.shape[2:])
+                for key, (p, mode) in (('tre_px', pred), ('tre_before_px', identity)):
+                    out[key] = (ops.map_points(p, mode, lm_B, src_hw, out_hw) - lm_A).norm(dim=2)
         return out
 
     def _netT_runs_at(self, h, w):

@@ -90,6 +90,16 @@ class AffineSTN(nn.Module):
         label maps.  No autograd."""
         return ops.warp_resampled(prediction_tensor(field), ops.GRID_AFFINE, list(imgs), out_hw, sample)
 
+    def overlap(self, field, labels_moving, labels_fixed, num_classes):
+        """Per-class overlap counts [N,K,3] (inter, moving, fixed) of labels_moving warped by the prediction — what
+        apply(..., sample='nearest') gives, never written — against labels_fixed at its size (ops.label_overlap).  No autograd."""
+        return ops.label_overlap(prediction_tensor(field), ops.GRID_AFFINE, labels_moving, labels_fixed, num_classes)
+
+    def map_points(self, field, pts, src_hw, out_hw):
+        """Where the prediction samples the src_hw source for points [N,P,2] (x, y) given in pixels of the out_hw fixed image
+        (ops.map_points).  No autograd."""
+        return ops.map_points(prediction_tensor(field), ops.GRID_AFFINE, pts, src_hw, out_hw)
+
     def fork_field(self, field, n_warps):
         """-> ([one theta handle per warp() call], the handle for regularization()) — ops.fork, as UnetSTN.fork_field"""
         hs = ops.fork(field, n_warps + 1)

@@ -1712,6 +1712,62 @@ def warp_resampled(pred, grid_mode, imgs, out_hw, sample='bilinear'):
     return outs
 
 
+def _prediction(what, pred, grid_mode):
+    """(contiguous detached prediction, N, hf, wf) of a read-out op that takes the STN's prediction as nemar_warp_resampled_fwd does"""
+    if grid_mode not in (GRID_UNET, GRID_AFFINE):
+        raise ValueError("%s: grid_mode %r (GRID_UNET or GRID_AFFINE)" % (what, grid_mode))
+    pred = _c(pred.detach())
+    N = pred.shape[0]
+    if not ((pred.dim() == 4 and pred.shape[1] == 2) if grid_mode == GRID_UNET else tuple(pred.shape) == (N, 6)):
+        raise ValueError("%s: prediction %s, expected [N,2,hf,wf] offsets or [N,6] dtheta" % (what, tuple(pred.shape)))
+    hf, wf = (int(pred.shape[2]), int(pred.shape[3])) if grid_mode == GRID_UNET else (0, 0)
+    return pred, N, hf, wf
+
+
+def _label_planes(what, labels, N):
+    """[N,H,W] or [N,1,H,W] -> contiguous float32 [N,H,W]"""
+    labels = labels.detach()
+    if labels.dim() == 4 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if labels.dim() != 3 or labels.shape[0] != N:
+        raise ValueError("%s: label map %s, expected [N,H,W] or [N,1,H,W] with N = %d" % (what, tuple(labels.shape), N))
+    return _c(labels.to(torch.float32))
+
+
+OVERLAP_COLUMNS = ('inter', 'moving', 'fixed')
+
+
+def label_overlap(pred, grid_mode, labels_moving, labels_fixed, num_classes):
+    """Segmentation overlap of a registration (nemar_label_overlap): labels_moving [N,Hs,Ws] (or [N,1,Hs,Ws]) warped by the prediction
+    with nearest sampling — exactly what warp_resampled(..., sample='nearest') returns, but never written — counted against
+    labels_fixed [N,Ho,Wo] at its size.  Returns an int32 [N,K,3] device tensor, columns OVERLAP_COLUMNS per class k: pixels where both
+    maps hold k, where the warped map does, where the fixed map does (Dice = 2 inter / (moving + fixed): the caller divides).  A value
+    that is no integer in [0, K) is counted on neither side; pixels warped from outside the source hold 0 and count as class 0.  An
+    identity prediction (GRID_AFFINE, zeros [N,6]) gives the overlap before registration.  No autograd, no sync."""
+    pred, N, hf, wf = _prediction("label_overlap", pred, grid_mode)
+    lm, lf = _label_planes("label_overlap", labels_moving, N), _label_planes("label_overlap", labels_fixed, N)
+    K = int(num_classes)
+    counts = torch.empty((N, K, 3), dtype=torch.int32, device=lf.device)
+    L.label_overlap(_p(lm), _p(lf), _p(pred), grid_mode, _p(counts), N, K, int(lm.shape[1]), int(lm.shape[2]), hf, wf,
+                    int(lf.shape[1]), int(lf.shape[2]), _stream())
+    return counts
+
+
+def map_points(pred, grid_mode, pts, src_hw, out_hw):
+    """The transformation at annotated points (nemar_map_points): pts [N,P,2] = (x, y) in pixels of the fixed image of size out_hw ->
+    [N,P,2], the position in pixels of the src_hw source that the warp samples there (the continuous extension of warp_resampled's
+    grid).  A NaN coordinate (a missing annotation) gives a NaN pair.  No autograd, no sync."""
+    pred, N, hf, wf = _prediction("map_points", pred, grid_mode)
+    pts = _c(pts.detach().to(torch.float32))
+    if pts.dim() != 3 or pts.shape[0] != N or pts.shape[2] != 2:
+        raise ValueError("map_points: points %s, expected [N,P,2] with N = %d" % (tuple(pts.shape), N))
+    out = torch.empty_like(pts)
+    if pts.shape[1]:
+        L.map_points(_p(pts), _p(pred), grid_mode, _p(out), N, int(pts.shape[1]), int(src_hw[0]), int(src_hw[1]), hf, wf,
+                     int(out_hw[0]), int(out_hw[1]), _stream())
+    return out
+
+
 # ---- known misalignment: ground-truth fields, the deforming input pipeline, the registration-error meter (no autograd: data and read-outs) ----
 def deform_field(params, B, Hc, Wc, gh, gw):
     """params [B, 6 + 2*gh*gw] (a11 a12 tx a21 a22 ty about the crop centre, then a [2,gh,gw] lattice of pixel displacements; gh = gw = 0:

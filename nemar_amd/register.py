@@ -4,7 +4,9 @@
         --stn_type unet --img_height 256 --img_width 256 --batch_size 4 --results_dir ./results
 
 DIR holds `A.npy` / `B.npy` in the format `--dataset_mode gpupairs` trains from ([M,3,H,W] or [M,H,W,3], uint8 or float in [0, 1]) and,
-optionally, `labels_A.npy` ([M,H,W] or [M,C,H,W], any numeric dtype: a label map of modality A at any size).  Every pair is brought to the
+optionally, `labels_A.npy` ([M,H,W] or [M,C,H,W], any numeric dtype: a label map of modality A at any size).  Something to score the
+result against is optional too: `labels_B.npy` ([M,H,W] or [M,1,H,W], the size of B.npy: the same classes in modality B) and
+`landmarks_A.npy` / `landmarks_B.npy` ([M,P,2] (x, y) in pixels of A.npy and B.npy: annotated point pairs, a NaN row = missing).  Every pair is brought to the
 network's --img_height x --img_width by the dataset's own resize and normalise path, netR predicts the transformation ONCE at that size
 (weights of --epoch under --checkpoints_dir/--name, the flags the model was trained with), and NEMARModel.register() applies it to the
 full-size images: the sampling grid is in normalised coordinates, so the prediction holds at every size (csrc/register.hip).
@@ -13,7 +15,12 @@ Written under --results_dir/--name/:
     registered_A.npy          modality A registered to B, in A.npy's own size, layout and dtype (uint8: rounded and clamped on the host)
     registered_labels_A.npy   labels_A.npy warped with nearest sampling (class ids are copied, never blended), in its own dtype
     offsets.npy               the network-resolution predictions: offsets [M,2,h,w] (unet) or dtheta [M,6] (affine)
-and one summary line on stdout: pairs, sizes, seconds."""
+    scores.json               only with labels_A.npy + labels_B.npy and / or the two landmark files (score_summary below): per-class and mean
+                              Dice before and after registration, from the counts of the whole data set; mean, median and max
+                              distance in pixels between the mapped landmarks of B and those of A, before and after, and how many
+                              point pairs were used
+and one summary line on stdout: pairs, sizes, the scores, seconds."""
+import json
 import os
 import time
 
@@ -50,6 +57,38 @@ def _like_input(t, ref, image):
     return a.astype(ref.dtype)
 
 
+def score_summary(overlap_before=None, overlap=None, tre_before=None, tre=None):
+    """What scores.json holds, from NEMARModel.register()'s score tensors of the whole data set (numpy; the batches concatenated along
+    the first axis): overlap* int [M,K,3] counts (inter, moving, fixed), tre* float [M,P] in pixels with NaN for a missing pair.
+    Dice per class is 2 * sum(inter) / (sum(moving) + sum(fixed)) with the sums over the data set — counts added, then divided —, over the
+    classes present in either map, before or after; TRE statistics are over the pairs that are present."""
+    scores = {}
+    if overlap is not None:
+        b, a = np.asarray(overlap_before, dtype=np.int64).sum(0), np.asarray(overlap, dtype=np.int64).sum(0)
+        present = np.flatnonzero((b[:, 1] + b[:, 2] + a[:, 1] + a[:, 2]) > 0)
+        dice = lambda c: [2.0 * int(c[k, 0]) / max(int(c[k, 1] + c[k, 2]), 1) for k in present]
+        d_b, d_a = dice(b), dice(a)
+        scores['dice'] = {'classes': [int(k) for k in present], 'before': d_b, 'after': d_a,
+                          'mean_before': float(np.mean(d_b)) if d_b else None, 'mean_after': float(np.mean(d_a)) if d_a else None}
+    if tre is not None:
+        t_b, t_a = np.asarray(tre_before, dtype=np.float64).ravel(), np.asarray(tre, dtype=np.float64).ravel()
+        used = np.isfinite(t_b) & np.isfinite(t_a)
+        stats = lambda t: {'mean': float(t.mean()), 'median': float(np.median(t)), 'max': float(t.max())} if t.size else None
+        scores['tre_px'] = {'points': int(used.sum()), 'before': stats(t_b[used]), 'after': stats(t_a[used])}
+    return scores
+
+
+def _optional(dataroot, name, M, what, ok):
+    """DIR/name if it exists, checked: `ok(array)` or exit with `what`"""
+    path = os.path.join(dataroot, name)
+    if not os.path.exists(path):
+        return None
+    a = np.load(path)
+    if a.shape[0] != M or not ok(a):
+        raise SystemExit('%s %s: %s with M = %d expected' % (name, a.shape, what, M))
+    return a
+
+
 def main(argv=None):
     opt = TestOptions().parse(argv, quiet=True)
     if not opt.gpu_ids:
@@ -70,18 +109,37 @@ def main(argv=None):
         if lab.ndim != 4 or lab.shape[0] != pool_A.shape[0]:
             raise SystemExit('labels_A.npy %s: [M,H,W] or [M,C,H,W] with M = %d expected' % (raw_labels.shape, pool_A.shape[0]))
         labels = torch.from_numpy(np.ascontiguousarray(lab).astype(np.float32)).to(device)
+    M = pool_A.shape[0]
+    # what to score against (scores.json): modality B's label map, annotated point pairs
+    raw_labels_B = _optional(opt.dataroot, 'labels_B.npy', M, '[M,H,W] or [M,1,H,W] of B.npy\'s size',
+                             lambda a: (a.ndim == 3 or (a.ndim == 4 and a.shape[1] == 1)) and tuple(a.shape[-2:]) == tuple(pool_B.shape[2:]))
+    raw_lm = [_optional(opt.dataroot, n, M, '[M,P,2]', lambda a: a.ndim == 3 and a.shape[2] == 2) for n in ('landmarks_A.npy', 'landmarks_B.npy')]
+    labels_B = lm_A = lm_B = num_classes = None
+    if raw_labels_B is not None and labels is not None:
+        if labels.shape[1] != 1:
+            raise SystemExit('labels_A.npy %s: a single-channel map is needed to score it against labels_B.npy' % (raw_labels.shape,))
+        labels_B = torch.from_numpy(np.ascontiguousarray(raw_labels_B.reshape(M, 1, *raw_labels_B.shape[-2:])).astype(np.float32)).to(device)
+        num_classes = int(max(np.nanmax(raw_labels), np.nanmax(raw_labels_B))) + 1      # one K for every batch: the counts are added
+    if raw_lm[0] is not None and raw_lm[1] is not None:
+        if raw_lm[0].shape != raw_lm[1].shape:
+            raise SystemExit('landmarks_A.npy %s and landmarks_B.npy %s: point pairs expected' % (raw_lm[0].shape, raw_lm[1].shape))
+        lm_A, lm_B = (torch.from_numpy(np.ascontiguousarray(a).astype(np.float32)).to(device) for a in raw_lm)
+    scored = {k: [] for k in ('overlap_before', 'overlap', 'tre_before_px', 'tre_px')}
     model = create_model(opt)
     model.setup(opt)
     if opt.eval:
         model.eval()
-    M = pool_A.shape[0]
     reg, reg_labels, offsets = [], [], []
     for i0 in range(0, M, opt.batch_size):
         idx = list(range(i0, min(M, i0 + opt.batch_size)))
         model.set_input(network_batch(pool_A, pool_B, idx, opt))
         model.test()
-        out = model.register(pool_A[idx[0]:idx[-1] + 1], pool_B[idx[0]:idx[-1] + 1], None if labels is None else labels[idx[0]:idx[-1] + 1],
-                             translate=False)          # (fake_RT_B is not among the files this command writes)
+        part = lambda t: None if t is None else t[idx[0]:idx[-1] + 1]
+        out = model.register(part(pool_A), part(pool_B), part(labels), translate=False,          # (fake_RT_B is not among the files this command writes)
+                             labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes)
+        for k in scored:
+            if k in out:
+                scored[k].append(out[k])
         reg.append(out['registered_A'])
         offsets.append(out['offsets'].clone())
         if labels is not None:
@@ -92,10 +150,20 @@ def main(argv=None):
     np.save(os.path.join(out_dir, 'offsets.npy'), torch.cat(offsets).cpu().numpy())
     if labels is not None:
         np.save(os.path.join(out_dir, 'registered_labels_A.npy'), _like_input(torch.cat(reg_labels), raw_labels, False))
+    told = ''
+    if scored['overlap'] or scored['tre_px']:
+        host = {k: torch.cat(v).cpu().numpy() if v else None for k, v in scored.items()}
+        scores = score_summary(host['overlap_before'], host['overlap'], host['tre_before_px'], host['tre_px'])
+        with open(os.path.join(out_dir, 'scores.json'), 'w') as f:
+            json.dump(scores, f, indent=1)
+        if scores.get('dice', {}).get('classes'):
+            told += ', mean Dice %.4f -> %.4f over %d classes' % (scores['dice']['mean_before'], scores['dice']['mean_after'], len(scores['dice']['classes']))
+        if scores.get('tre_px', {}).get('points'):
+            told += ', mean TRE %.3f -> %.3f px over %d points' % (scores['tre_px']['before']['mean'], scores['tre_px']['after']['mean'], scores['tre_px']['points'])
     torch.cuda.synchronize()
-    print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s, %.2f s -> %s'
+    print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s, %.2f s -> %s'
           % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width,
-             '' if labels is None else ', labels %dx%d' % tuple(labels.shape[2:]), time.time() - t0, out_dir))
+             '' if labels is None else ', labels %dx%d' % tuple(labels.shape[2:]), told, time.time() - t0, out_dir))
 
 
 if __name__ == '__main__':
