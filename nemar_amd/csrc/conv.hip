@@ -1,28 +1,18 @@
-// K1 + K2 + K4 + K8: the convolution operators — entry points, routing, workspace layouts.
+// K1 + K2 + K4 + K8: the convolution operators — entry points, launches, and the kernels that live here.
 //
-// Replaces nn.Conv2d / nn.ConvTranspose2d (+ the ReflectionPad2d in front of them and the torch.cat that
-// feeds them) at reference models/networks.py:349-377,418-439,576-597 and models/stn/layers.py:85,
-// models/stn/unet_stn.py:80,97, models/stn/affine_stn.py:69-72,79 — forward, data gradient and weight
-// gradient.  nn.Linear of the affine head is the 1x1 case on a 1x1 image.
+// Replaces nn.Conv2d / nn.ConvTranspose2d (+ the ReflectionPad2d in front of them and the torch.cat that feeds them) at reference
+// models/networks.py:349-377,418-439,576-597 and models/stn/layers.py:85, models/stn/unet_stn.py:80,97, models/stn/affine_stn.py:69-72,79 —
+// forward, data gradient and weight gradient.  nn.Linear of the affine head is the 1x1 case on a 1x1 image.
 //
-// Each call is routed to one kernel family (nemar_last_route): the 16-bit-pipe kernels with fp32-accurate split operands
-// (conv_split16*.hip: the wide residual-block layers; conv_s16g*.hip: general layers; conv_k7.hip: the 7x7 stem / head), the VALU
-// kernels for <= 4 channels (conv_narrow.hip), or the exact-fp32 tap-table implicit GEMM (conv_exact.hip), which serves forward AND
-// data gradient (and therefore ConvTranspose2d, the data gradient of a strided conv):
-//   - a stride-2 data-gradient is four launches, one per output-pixel parity class, each with the subset of
-//     taps that lands on integer source positions;
-//   - a stride-1 reflect data-gradient is the zero-padded data-gradient on the unpadded domain plus a small launch over
-//     the border ring whose results are added to the texels the padding mirrored (nemar_conv2d_bwd_data).
-//
-// The weight gradient is a second implicit GEMM, dW[k][c,r,s] = sum_pixels gy[k,p] * src[c, p (+) tap], with
-// the (huge) pixel reduction split across workgroups into per-split slabs summed in order:
-// conv_wgrad.hip (wave-specialised) for everything whose gy planes are 16-byte chunkable, wgrad_kernel below for the rest.
+// Each operator is: validate -> plan (conv_route.h: which kernel family serves the call, with which workspace layout; the table is DESIGN.md
+// 4a) -> workspace check -> switch on the plan, where each case only fills parameters and launches.  The host-side size queries at the end of
+// the file ask the same plans with the canonical call-time facts.  Kernels here: the first-generation weight gradient (wgrad_kernel: what
+// conv_wgrad.hip does not take), the passes around the exact-fp32 reflect data gradient, bias gradients, and the 7x7 many -> few passes.
+#define NEMAR_CONV_HIP
 #include "common.h"
 #include "conv_exact.h"
 #include "conv_call.h"
-#include "conv_split16.h"
-#include "conv_s16g.h"
-#include "conv_k7.h"
+#include "conv_route.h"
 #include "pack_plan.h"
 
 #ifdef NEMAR_AB
@@ -36,16 +26,11 @@ void nemar_norm_planes_debug(int bits);          // norm_planes.hip: ablation bi
 #endif
 
 // conv_narrow.hip: VALU + LDS-halo kernels for layers with <= 4 output channels
-bool nemar_narrow_eligible(int K, int C1, int R, int S, int stride, int N, int OH, int OW);
 int nemar_narrow_fwd(const float* x, const float* w, const float* bias, float* y, int N, int C, int H, int W, int K, int R,
                      int pad, int border, int act, float slope, float* part, size_t part_floats, hipStream_t st);
-int nemar_narrow_wgrad_splits(int N, int C, int OH, int OW);
 int nemar_narrow_wgrad(const float* x, const float* gy, float* gw, int N, int C, int H, int W, int K, int R, int pad,
                        int border, float* part, hipStream_t st);
-
 // conv_wgrad.hip: wave-specialised weight gradient for wide layers
-bool nemar_wgrad2_eligible(int K, int OH, int OW, const float* gy);
-void nemar_wgrad2_plan(int K, int J, int P, int target_blocks, int* splits_out, int* pix_per_split_out);
 void nemar_wgrad2_launch(const float* x0, int C0, const float* x1, int C1, const float* gy, float* gw, float* gb, int N,
                          int H, int W, int K, int OH, int OW, int R, int S, int stride, int pad, int pad_mode,
                          int target_blocks, bool vec_ok, int dbg, float* part, hipStream_t st);
@@ -57,45 +42,14 @@ void nemar_sum_partials_fold(const float* part, long long stride, int splits, fl
 void nemar_sum_partials(const float* part, long long stride, int splits, float* dst, long long n, bool accumulate,
                         hipStream_t st);
 
-using namespace nemar_exact;
-
 namespace {
 
-// key 20: 3x3 / stride-1 layers with >= 128 output channels run on the bf16 matrix pipe with three-way split operands
-// (conv_split16.hip) whenever the call brings a scratch arena large enough for the split source planes
-static NEMAR_SWITCH(int, g_split16, 1);
-// key 23: the split-16 route needs work to amortise its extra launches (max pass, split pass, slab sum): layers below this many
-// million multiply-adds (default 2000 = 4 GFLOP, ~40 us on the exact-fp32 kernels) stay on those — BASELINE config 1's 32x32
-// batch-1 resblocks (0.6 GMAC) lost 2 ms per step to launch overhead on the split-16 route
-static NEMAR_SWITCH(long long, g_split16_min_mmac, 2000);
-static NEMAR_SWITCH(int, g_split16_variant, 4);   // key 21: 4 fp16 x 3 products (default), 3 bf16 x 6 products, 0 bf16 x 6 on the first-generation
-                                // kernel with loader waves (kept for the A/B numbers in DESIGN.md)
-// which kernel family served the last conv call of this thread (nemar_last_route; tests and tools): 0 exact-fp32 implicit GEMM,
-// 1 narrow (<= 4 channel) VALU kernels, 2 split-16 kernel of the wide residual-block layers, 3 general 16-bit-pipe kernels
+// which kernel family served the last conv call of this thread (nemar_last_route; tests and tools): conv_route.h ROUTE_*
 static thread_local int g_last_route = 0;
 static thread_local int g_last_gy_planes = 0;     // did the last nemar_conv2d_bwd_data_ex call of this thread fill gy_planes_out? (nemar_last_gy_planes)
 static NEMAR_SWITCH(int, g_config_epoch, 0);      // A/B build: bumped by every nemar_tune (routes and packed-weight formats may have changed)
-static NEMAR_SWITCH(int, g_k7, 1);               // key 33: the 7x7 stem / head layers (<= 4 channels on one side) on the 16-bit matrix pipe (conv_k7.hip)
-static NEMAR_SWITCH(int, g_s16g, 1);             // key 24: general layers on the 16-bit matrix pipe with the in-kernel operand split (conv_s16g.hip)
-static NEMAR_SWITCH(int, g_s16g_wgrad_first, 0);  // key 26: 1 = the in-kernel-split weight gradient also takes the wide residual-block layers (stand-alone 374 vs
-                                    // 393 us per call, but 44.3 vs 41.8 ms per step inside the bench: off)
-static NEMAR_SWITCH(int, g_s16g_wgrad, 1);        // key 29: weight gradients on the in-kernel-split kernels (conv_s16g_wgrad.hip)
-static NEMAR_SWITCH(int, g_s16g_fold, 1);         // key 30: stride-1 reflect data gradients on the padded domain + fold
-static NEMAR_SWITCH(long long, g_s16g_min_mmac, 30);   // key 25: ... above this many million multiply-adds (tiny layers are launch-bound either way)
-static NEMAR_SWITCH(int, g_split_act, 1);          // key 36: reduction-split forward layers with a fused ReLU / LeakyReLU (activation in the sum pass)
-static NEMAR_SWITCH(int, g_fold_small, 1);         // key 43: stride-1 reflect data gradients of tiny maps on the exact route: padded domain + sum-and-fold pass
-static NEMAR_SWITCH(int, g_dual_gy, 1);            // key 35: the data-gradient call's split pass also writes the weight gradient's gy planes
-static NEMAR_SWITCH(int, g_reflect_aux, 1);    // tuning switch (key 8): 3x3 reflect data gradient folds the border into the main launch (1) / ring launch (0)
-static NEMAR_SWITCH(int, g_deterministic, 1);  // tuning switch (key 14): 1 = split reductions go through per-split slabs summed in order (bitwise
-                                 // reproducible backward pass), 0 = fp32 atomics in the weight / bias gradients (round-1 scheme)
-static NEMAR_SWITCH(int, g_ksplit, 1);         // tuning switch (key 12): allow reduction splits in the wave-specialised data gradient
-static NEMAR_SWITCH(int, g_narrow, 1);   // tuning switch (key 3): route <=4-channel layers to the VALU kernels
-static NEMAR_SWITCH(int, g_wgrad, 0);    // tuning switch (key 4): 0 = wave-specialised wide weight gradient, 1 = VGPR-staged kernel, 2 = wave-specialised without 16-byte source loads
-static NEMAR_SWITCH(int, g_wgrad_blocks, 512);   // tuning switch (key 5): workgroups targeted by the pixel split
 
 // ---- weight gradient ----------------------------------------------------------------------------------------
-constexpr int WBK = 32;  // pixels per LDS stage
-
 struct WgradParams {
     const float* src0; const float* src1; int C0, C1, Hs, Ws;
     const float* gy; int K, OH, OW;
@@ -433,6 +387,15 @@ __global__ __launch_bounds__(256) void bias_grad_kernel(const float* __restrict_
     if (threadIdx.x == 0) part[((size_t)n * gridDim.z + blockIdx.z) * C + c] = t;
 }
 
+// gb[C] += sum over N and the plane of g [N,C,HW]: through the partial sums of bias_grad_kernel at `part`, or (no slabs) by atomics — the
+// bias gradient of every route whose kernels leave gb alone, and nemar_bias_grad
+void bias_grad_slabs(const float* g, float* gb, float* part, int N, int C, int HW, hipStream_t st) {
+    const int chunks = nemar_cdiv(HW, BIAS_CHUNK);
+    if (!part) { hipLaunchKernelGGL(bias_grad_atomic_kernel, dim3(C, N, chunks), dim3(256), 0, st, g, gb, N, C, HW, BIAS_CHUNK); return; }
+    hipLaunchKernelGGL(bias_grad_kernel, dim3(C, N, chunks), dim3(256), 0, st, g, part, N, C, HW, BIAS_CHUNK);
+    nemar_sum_partials(part, C, N * chunks, gb, C, true, st);
+}
+
 // gx[n,c,h,w] = sum of the padded-domain gradient gp over every padded position that mirrors onto (h,w)
 // (+ addend[n,c,h,w] where given: the skip gradient of a ResnetBlock rides in the pass that writes the data gradient of its first convolution)
 __global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restrict__ gp, float* __restrict__ gx, int H,
@@ -463,113 +426,12 @@ __global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restri
         gx[idx] = addend ? s + addend[idx] : s;
     }
 }
-
-// Reduction split for tiny, deep problems on the generic kernels (the launch would otherwise be a handful of workgroups
-// each walking the whole reduction at memory latency): enough splits for ~256 workgroups, >= 4 stages each.
-int small_problem_split(int M, int P, int Kred) {
-    const TileChoice t = igemm_tile(M, P, nemar_cdiv(Kred, BK));
-    if (t.bm == 128) return 1;
-    const long long tiles = (long long)nemar_cdiv(M, t.bm) * nemar_cdiv(P, t.bn);
-    const int stages = nemar_cdiv(Kred, BK);
-    if (tiles >= 128 || stages < 16) return 1;
-    int ks = nemar_cdiv(256, (int)tiles);
-    if (ks > stages / 4) ks = stages / 4;
-    return ks < 1 ? 1 : ks;
+// the padded domain's gradient folded onto the image (+ addend)
+void fold_padded(const float* padded, float* gx, int H, int W, int pad, long long total, const float* addend, hipStream_t st) {
+    hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, padded, gx, H, W, pad, total, addend);
 }
 
-void fwd_taps(TapTable& t, int R, int S, int pad) {
-    t.n = R * S;
-    for (int r = 0; r < R; ++r)
-        for (int s = 0; s < S; ++s) {
-            t.dy[r * S + s] = (short)(r - pad);
-            t.dx[r * S + s] = (short)(s - pad);
-            t.dyx[r * S + s] = ((r - pad) << 16) | ((s - pad) & 0xffff);
-            t.wofs[r * S + s] = r * S + s;
-        }
-}
-
-// taps of output-pixel parity class (ph, pw) of a stride-`stride` data gradient: r with (ph + pad - r) % stride == 0
-void dgrad_taps(TapTable& t, int R, int S, int pad, int stride, int ph, int pw) {
-    t.n = 0;
-    for (int r = 0; r < R; ++r) {
-        if ((ph + pad - r) % stride != 0) continue;
-        for (int s = 0; s < S; ++s) {
-            if ((pw + pad - s) % stride != 0) continue;
-            t.dy[t.n] = (short)((ph + pad - r) / stride);
-            t.dx[t.n] = (short)((pw + pad - s) / stride);
-            t.dyx[t.n] = ((int)t.dy[t.n] << 16) | ((int)t.dx[t.n] & 0xffff);
-            t.wofs[t.n] = r * S + s;
-            t.n++;
-        }
-    }
-}
-
-
-// every split of a reduction must own at least one stage (its slab is summed unconditionally)
-int normalize_ksplit(int Kred, int ksplit) {
-    if (ksplit <= 1) return 1;
-    const int nk_all = nemar_cdiv(Kred, BK);
-    const int nk_per = nemar_cdiv(nk_all, ksplit);
-    return nemar_cdiv(nk_all, nk_per);
-}
-
-static bool split16_worth_it(int N, int OH, int OW, int K, int C, int R, int S) {
-    return (long long)N * OH * OW * K * C * R * S >= g_split16_min_mmac * 1000000ll;
-}
-
-// ---- routing to conv_s16g.hip (general layers on the 16-bit matrix pipe) ------------------------------------------------------
-void s16g_set_class(S16gProblem& q, int c, const TapTable& t, int OHc, int OWc, int ooy, int oox) {
-    q.ntaps[c] = t.n;
-    for (int i = 0; i < t.n && i < S16G_MAX_TAPS; ++i) { q.dy[c][i] = t.dy[i]; q.dx[c][i] = t.dx[i]; q.wofs[c][i] = t.wofs[i]; }
-    q.OH[c] = OHc; q.OW[c] = OWc; q.ooy[c] = ooy; q.oox[c] = oox;
-}
-bool s16g_worth_it(long long macs) { return g_s16g && macs >= g_s16g_min_mmac * 1000000ll; }
-
-// forward: geometry only (pointers are filled by the operator); false = not this route
-bool s16g_fwd_problem(S16gProblem& q, S16gPlan& pl, int N, int C0, int C1, int H, int W, int K, int R, int S, int stride, int pad,
-                      int pad_mode, int act, float slope) {
-    const int C = C0 + C1;
-    if (R * S > S16G_MAX_TAPS || stride > 2 || stride < 1) return false;
-    const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-    if (OH <= 0 || OW <= 0 || !s16g_worth_it((long long)N * OH * OW * K * C * R * S)) return false;
-    q = S16gProblem();
-    q.C0 = C0; q.C1 = C1; q.Hs = H; q.Ws = W; q.N = N; q.M = K; q.M0 = K;
-    q.act = act; q.slope = slope; q.border = pad_mode; q.sstride = stride;
-    q.OHf = OH; q.OWf = OW; q.osy = 1; q.osx = 1; q.ncls = 1;
-    TapTable t;
-    fwd_taps(t, R, S, pad);
-    s16g_set_class(q, 0, t, OH, OW, 0, 0);
-    pl = nemar_s16g_plan(q);
-    return pl.ok != 0;
-}
-
-// data gradient / transposed convolution (zero padding): one class per output parity
-bool s16g_dgrad_problem(S16gProblem& q, S16gPlan& pl, int N, int C, int mskip, int H, int W, int K, int OH, int OW, int R, int S,
-                        int stride, int pad, int act, float slope) {
-    if (R * S > S16G_MAX_TAPS || stride > 2 || stride < 1) return false;
-    if (!s16g_worth_it((long long)N * OH * OW * K * (C - mskip) * R * S)) return false;
-    q = S16gProblem();
-    q.C0 = K; q.C1 = 0; q.Hs = OH; q.Ws = OW; q.N = N; q.M = C - mskip;
-    q.act = act; q.slope = slope; q.border = BORDER_ZERO; q.sstride = 1;
-    q.OHf = H; q.OWf = W; q.osy = stride; q.osx = stride; q.ncls = 0;
-    for (int ph = 0; ph < stride; ++ph)
-        for (int pw = 0; pw < stride; ++pw) {
-            TapTable t;
-            dgrad_taps(t, R, S, pad, stride, ph, pw);
-            const int OHc = (H - ph + stride - 1) / stride, OWc = (W - pw + stride - 1) / stride;
-            if (t.n == 0 || OHc <= 0 || OWc <= 0 || t.n > (stride > 1 ? S16G_CLS_TAPS : S16G_MAX_TAPS)) return false;
-            s16g_set_class(q, q.ncls++, t, OHc, OWc, ph, pw);
-        }
-    pl = nemar_s16g_plan(q);
-    return pl.ok != 0;
-}
-
-// ---- 7x7 / pad-3 layers with <= 4 channels on the OUTPUT side (the translation net's RGB head; the data gradient of its stem) -------
-// out[k][y][x] = sum_{c, dy, dx} w[k][c][dy][dx] src[c][y + dy][x + dx] with 3 rows would waste 29 of 32 MFMA rows.  Instead the rows of the
-// GEMM are the (k, dx) PAIRS (4 x 8 = 32 pseudo-channels): P[(k, dx)][y][x'] = sum_{c, dy} w[k][c][dy][dx] src[c][y + dy][x'] is a SEVEN-TAP
-// VERTICAL convolution with 32 output channels — the general 16-bit-pipe kernel (conv_s16g.hip) takes it as it is, over the halo columns
-// x' as well — and out[k][y][x] = sum_dx P[(k, dx)][y][x + dx] is a horizontal shift-sum (k7_mf_sum_kernel: + bias, activation, and
-// for a reflect-padded data gradient the fold of the padded domain).  Workspace: [re-arranged weights][their packed image][P].
+// ---- 7x7 / pad-3 layers with <= 4 channels on the OUTPUT side: the launches of the many -> few form (conv_route.h K7MfPlan) ----------
 __global__ __launch_bounds__(256) void k7_mf_weights_kernel(const float* __restrict__ w, float* __restrict__ wt, int Ks, int Cb, int dgrad) {
     // wt[(ks * 8 + dx)][cb][dy]: forward w[ks][cb][dy][dx] (w = [Ks][Cb][7][7]); data gradient w[cb][ks][6 - dy][6 - dx] (w = [Cb][Ks][7][7])
     const int total = 32 * Cb * 7;
@@ -647,41 +509,6 @@ __global__ __launch_bounds__(256) void k7_mf_sum_kernel(const float* __restrict_
     }
 }
 
-// geometry of the vertical convolution: P = [N][32][PH][PW]; src = [N][Cb][Hs][Ws] seen through a border of `spad` (3: forward / zero-padded
-// gradient; 6, zero: reflect gradient on the padded domain)
-struct K7MfPlan {
-    S16gProblem q;
-    S16gPlan pl;
-    size_t wt_off, pack_off, p_off, total;      // floats
-    int PH, PW;
-    bool ok;
-};
-K7MfPlan k7_mf_plan(int N, int Cb, int Hs, int Ws, int spad, int border) {
-    K7MfPlan m;
-    m.ok = false;
-    m.PH = Hs + 2 * spad - 6;
-    m.PW = Ws + 2 * spad;
-    S16gProblem& q = m.q;
-    q = S16gProblem();
-    q.C0 = Cb; q.C1 = 0; q.Hs = Hs; q.Ws = Ws; q.N = N; q.M = 32; q.M0 = 32;
-    q.act = ACT_NONE; q.slope = 0.f; q.border = border; q.sstride = 1;
-    q.OHf = m.PH; q.OWf = m.PW; q.osy = 1; q.osx = 1; q.ncls = 1;
-    TapTable t;
-    t.n = 7;
-    for (int i = 0; i < 7; ++i) { t.dy[i] = (short)(i - spad); t.dx[i] = (short)(-spad); t.dyx[i] = ((i - spad) << 16) | ((-spad) & 0xffff); t.wofs[i] = i; }
-    s16g_set_class(q, 0, t, m.PH, m.PW, 0, 0);
-    m.pl = nemar_s16g_plan(q);
-    if (!m.pl.ok) return m;
-    m.wt_off = 0;
-    m.pack_off = ((size_t)32 * Cb * 7 + 3) & ~(size_t)3;
-    m.p_off = (m.pack_off + (nemar_s16g_pack_bytes(q, m.pl) + 3) / 4 + 3) & ~(size_t)3;
-    m.total = m.p_off + (size_t)N * 32 * m.PH * m.PW;
-    m.ok = true;
-    return m;
-}
-bool k7_mf_eligible(int Cb, int Ks, int R, int S, int stride, int pad) {
-    return g_k7 && R == 7 && S == 7 && stride == 1 && pad == 3 && Ks >= 1 && Ks <= 4 && Cb >= 16 && Cb % 16 == 0;
-}
 // src -> out through the three launches (weights re-arranged + packed first unless prepacked)
 void k7_mf_run(const K7MfPlan& m_, const float* src, const float* w, int Ks, int Cb, int dgrad, const float* bias, float* out, int N, int H, int W,
                int fold, int act, float slope, float* wsf, int prepacked, hipStream_t st) {
@@ -702,148 +529,29 @@ void k7_mf_run(const K7MfPlan& m_, const float* src, const float* w, int Ks, int
                        act, slope, total);
 }
 
-// Workspace layout of nemar_conv2d_bwd_data (floats), shared by the size query and the operator:
-//   [packed weights x stride^2 parity classes][padded-domain scratch (strided reflect)][flipped weights (C <= 4)]
-//   [compact border-ring gradient (stride-1 reflect)][ksplit slabs of the gradient (split reductions)]
-struct DgradLayout {
-    size_t pack_stride, padded_off, w2_off, ring_off, ring_slab_off, slab_off, aux_rows_off, aux_cols_off, total;
-    int ring_len, ksplit, ring_ksplit;
-    bool ring, fold, fold16, fold_small;
-};
-DgradLayout dgrad_layout(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
-    DgradLayout L;
-    const bool refl = pad_mode == BORDER_REFLECT && pad > 0;
-    L.ring = refl && stride == 1;
-    L.fold = refl && !L.ring;
-    L.pack_stride = packed_floats(C, K * R * S);             // upper bound over parity classes and channel skips
-    if (nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, SPLIT16_ZERO, 4)) {     // room for either packed image
-        const size_t b = (nemar_split16_pack_bytes(C, K, R) + 3) / 4;
-        if (b > L.pack_stride) L.pack_stride = b;
+// copy of gy with OHv >= OH rows per plane, (OHv * OW) % 4 == 0, zero-filled below row OH (conv_route.h padded_rows)
+__global__ __launch_bounds__(256) void pad_planes_kernel(const float* __restrict__ src, float* __restrict__ dst, int plane,
+                                                         int plane_padded, long long total) {
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const long long pl = idx / plane_padded;
+        const int r = (int)(idx - pl * plane_padded);
+        dst[idx] = r < plane ? src[pl * plane + r] : 0.f;
     }
-    {
-        S16gProblem q;
-        S16gPlan pl;
-        const int OHd = (H + 2 * pad - R) / stride + 1, OWd = (W + 2 * pad - S) / stride + 1;
-        if (!refl && OHd > 0 && OWd > 0 && s16g_dgrad_problem(q, pl, N, C, 0, H, W, K, OHd, OWd, R, S, stride, pad, ACT_NONE, 0.f)) {
-            const size_t b = ((nemar_s16g_pack_bytes(q, pl) + 3) / 4 + stride * stride - 1) / (stride * stride);
-            if (b > L.pack_stride) L.pack_stride = b;
-        }
-    }
-    // stride-1 reflect layers the general 16-bit-pipe kernel takes: the data gradient of the PADDED input (a plain zero-padded full
-    // correlation on the (H + 2p) x (W + 2p) domain) into scratch, then the fold — one extra pass over the gradient, but the
-    // implicit GEMM runs at several times the exact-fp32 rate (R net: 175 -> ~95 us per call)
-    L.fold16 = false;
-    if (L.ring && g_s16g_fold && R * S <= 9) {          // (49-tap layers: the 32-row tile would cost more than it saves)
-        S16gProblem q;
-        S16gPlan pl;
-        const int OHd = H + 2 * pad - R + 1, OWd = W + 2 * pad - S + 1;
-        if (OHd > 0 && OWd > 0 && s16g_dgrad_problem(q, pl, N, C, 0, H + 2 * pad, W + 2 * pad, K, OHd, OWd, R, S, 1, 0, ACT_NONE, 0.f)) {
-            L.fold16 = true;
-            const size_t b = (nemar_s16g_pack_bytes(q, pl) + 3) / 4;
-            if (b > L.pack_stride) L.pack_stride = b;
-        }
-    }
-    // Tiny stride-1 reflect layers that stay on the exact-fp32 kernels (the <= 16 x 16 maps of the registration net's ResnetBlocks): the
-    // padded-domain form as well — ONE implicit-GEMM launch over the (H + 2p) x (W + 2p) domain with its reduction split into slabs, then ONE
-    // pass that sums the slabs and folds the mirrored border (nemar_sum_partials_fold).  The ring form of the same layer is five
-    // launches of 4 - 8 us each on the step's critical chain: interior, its slab sum, border ring, its slab sum, gather.
-    L.fold_small = L.ring && !L.fold16 && g_fold_small && g_ksplit && C > 4 && (H + 2 * pad) * (W + 2 * pad) <= 1296;
-    if (L.fold_small) { L.ring = false; L.fold = true; }
-    size_t o = L.pack_stride * (size_t)(stride * stride);
-    L.padded_off = o;
-    if (L.fold || L.fold16) o += (size_t)N * C * (H + 2 * pad) * (W + 2 * pad);
-    L.w2_off = o;
-    if (C <= 4) o += (size_t)C * K * R * S;
-    L.ring_off = o;
-    L.ring_len = L.ring ? 2 * pad * (W + 2 * pad) + 2 * pad * H : 0;
-    o += (size_t)N * C * L.ring_len;
-    // a ring tile is a few pixels deep in a full-length reduction, and a lone workgroup per CU walks it at memory latency:
-    // the reduction is split until ~1.5 workgroups per CU exist (each split = one slab, summed in order)
-    L.ring_ksplit = 1;
-    L.ring_slab_off = o;
-    if (L.ring) {
-        const int tiles = nemar_cdiv(N * L.ring_len, 64) * nemar_cdiv(C, 64), stages = nemar_cdiv(K * R * S, BK);
-        int ks = nemar_cdiv(384, tiles);
-        if (ks > nemar_cdiv(stages, 8)) ks = nemar_cdiv(stages, 8);
-        L.ring_ksplit = normalize_ksplit(K * R * S, ks < 1 ? 1 : ks);
-        if (L.ring_ksplit > 1) o += (size_t)L.ring_ksplit * N * C * L.ring_len;
-    }
-    // split reductions (stride 1, single destination, no bias / activation — the operator re-checks those): few, deep
-    // 128x128 tiles (D's 256->512 k4 layer: 128 tiles x 512 stages) get one workgroup per CU; tiny deep problems on the
-    // generic kernels (the 2x2 .. 32x32-pixel layers of the registration net) ~256 workgroups of >= 4 stages
-    L.ksplit = 1;
-    const int Hs = L.fold_small ? H + 2 * pad : H, Wsl = L.fold_small ? W + 2 * pad : W;      // the domain the split launch covers
-    if (g_ksplit && stride == 1 && (!L.fold || L.fold_small) && C > 4) {
-        const int P = N * Hs * Wsl, Kred = K * R * S, stages = nemar_cdiv(Kred, BK);
-        if (g_cfg128 == 0 && C > 64 && K % BK == 0) {
-            const long long tiles = (long long)nemar_cdiv(C, 128) * nemar_cdiv(P, 128);
-            if (tiles < 200 && stages >= 256) {
-                int ks = nemar_cdiv(256, (int)tiles);
-                if (ks > stages / 128) ks = stages / 128;
-                if (ks > 1) L.ksplit = ks;
-            }
-        }
-        if (L.ksplit == 1) L.ksplit = small_problem_split(C, P, Kred);
-        L.ksplit = normalize_ksplit(Kred, L.ksplit);
-    }
-    L.slab_off = o;
-    if (L.ksplit > 1) o += (size_t)L.ksplit * N * C * Hs * Wsl;
-    // side buffers of the ring-free reflect data gradient (source = gy [N,K,H,W] for a 3x3 / pad 1 layer)
-    L.aux_rows_off = o;
-    if (L.ring && pad == 1 && R == 3 && S == 3) o += 6ull * N * K * W;
-    L.aux_cols_off = o;
-    if (L.ring && pad == 1 && R == 3 && S == 3) o += 8ull * N * K * H;
-    L.total = o;
-    if (k7_mf_eligible(K, C, R, S, stride, pad)) {                       // 7x7 stem (<= 4 input channels): [re-arranged weights | packed image | P]
-        const K7MfPlan m = k7_mf_plan(N, K, H, W, refl ? 6 : 3, BORDER_ZERO);
-        if (m.ok && m.total > L.total) L.total = m.total;
-    }
-    if (C > 4 && nemar_k7_fm_eligible(K, C, R, S, stride, pad)) {       // 7x7 head (<= 4 output channels): [packed weights | padded-domain gradient]
-        const size_t k7 = ((nemar_k7_fm_pack_floats(C) + 3) & ~(size_t)3) + (refl ? (size_t)N * C * (H + 6) * (W + 6) : 0);
-        if (k7 > L.total) L.total = k7;
-    }
-    return L;
-}
-
-
-// Workspace of nemar_conv2d_fwd (floats): [packed weights][slabs of a split reduction].  Tiny, deep layers (the 2x2 .. 32x32
-// maps of the registration net: a 2x2-pixel 128->128 3x3 layer is 72 serial stages in two workgroups) split their reduction
-// like the data gradients do; per-split slabs summed in order keep the forward pass bitwise reproducible.
-struct FwdLayout { size_t pack, slab_off, total; int ksplit; };
-FwdLayout fwd_layout(int N, int H, int W, int K, int C, int R, int S, int stride, int pad) {
-    FwdLayout L;
-    L.pack = packed_floats(K, C * R * S);
-    if (nemar_split16_eligible(N, H, W, K, C, R, S, stride, pad, SPLIT16_ZERO, 4)) {     // room for either packed image
-        const size_t b = (nemar_split16_pack_bytes(K, C, R) + 3) / 4;
-        if (b > L.pack) L.pack = b;
-    }
-    {
-        S16gProblem q;
-        S16gPlan pl;
-        if (s16g_fwd_problem(q, pl, N, C, 0, H, W, K, R, S, stride, pad, BORDER_ZERO, ACT_NONE, 0.f)) {
-            const size_t b = (nemar_s16g_pack_bytes(q, pl) + 3) / 4;
-            if (b > L.pack) L.pack = b;
-        }
-    }
-    if (nemar_k7_fm_eligible(C, K, R, S, stride, pad) && nemar_k7_fm_pack_floats(K) > L.pack) L.pack = nemar_k7_fm_pack_floats(K);
-    L.ksplit = 1;
-    const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-    if (g_ksplit && OH > 0 && OW > 0 && K > 4) L.ksplit = normalize_ksplit(C * R * S, small_problem_split(K, N * OH * OW, C * R * S));
-    L.slab_off = (L.pack + 3) & ~(size_t)3;
-    L.total = L.slab_off + (L.ksplit > 1 ? (size_t)L.ksplit * N * K * OH * OW : 0);
-    if (k7_mf_eligible(C, K, R, S, stride, pad)) {           // 7x7 head: [re-arranged weights | packed image | P] (either border)
-        const K7MfPlan m = k7_mf_plan(N, C, H, W, 3, BORDER_ZERO);
-        if (m.ok && m.total > L.total) L.total = m.total;
-    }
-    return L;
 }
 
 }  // namespace
 
-// ------------------------------------------------------------------------------------------------------------
+// the call-time facts every operator has
+static ConvFacts facts_of(const ConvCall& call, const float* bias, int act, float slope) {
+    ConvFacts f;
+    f.bias = bias != nullptr; f.act = act; f.slope = slope; f.scratch_bytes = call.scratch ? call.scratch_bytes : 0;
+    return f;
+}
+
 NEMAR_API size_t nemar_conv2d_fwd_workspace(int N, int H, int W, int K, int C, int R, int S, int stride, int pad) {
     if (N <= 0 || H <= 0 || W <= 0 || K <= 0 || C <= 0 || R <= 0 || S <= 0 || stride < 1) return 0;
-    return sizeof(float) * fwd_layout(N, H, W, K, C, R, S, stride, pad).total;
+    return sizeof(float) * plan_fwd({N, C, 0, H, W, K, R, S, stride, pad, BORDER_ZERO}, ConvFacts::canonical()).total;
 }
 
 // Honours call.scratch, .src_max and .src_planes (the wide route)
@@ -860,110 +568,86 @@ static int conv2d_fwd(ConvCall& call, const float* x0, int C0, const float* x1, 
     const int C = C0 + C1;
     const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
     NEMAR_REQUIRE(OH > 0 && OW > 0, "conv2d_fwd: empty output");
-    NEMAR_REQUIRE((long long)N * OH * OW < (1ll << 31) && (long long)C * H * W < (1ll << 31) &&
-                      (long long)C * R * S < (1 << 20),
+    NEMAR_REQUIRE((long long)N * OH * OW < (1ll << 31) && (long long)C * H * W < (1ll << 31) && (long long)C * R * S < (1 << 20),
                   "conv2d_fwd: problem too large for 32-bit tile indexing");
-    const FwdLayout FL = fwd_layout(N, H, W, K, C, R, S, stride, pad);
-    const size_t need = sizeof(float) * FL.total;
-    if (ws_bytes < need) {
-        nemar_set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, need);
+    ConvFacts f = facts_of(call, bias, act, slope);
+    FwdPlan P = plan_fwd({N, C0, C1, H, W, K, R, S, stride, pad, pad_mode}, f);
+    if (ws_bytes < sizeof(float) * P.total) {
+        nemar_set_error("conv2d_fwd: workspace %zu < %zu", ws_bytes, sizeof(float) * P.total);
         return NEMAR_EWORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    if (C1 == 0 && k7_mf_eligible(C, K, R, S, stride, pad)) {
-        // 7x7 head (<= 4 output channels): vertical 7-tap convolution with (k, dx) pseudo-channels on the general 16-bit-pipe kernel, then
-        // the horizontal shift-sum with bias and activation (tanh included)
-        const K7MfPlan m = k7_mf_plan(N, C, H, W, 3, pad_mode);
-        if (m.ok) {
-            k7_mf_run(m, x0, w, K, C, 0, bias, y, N, H, W, 0, act, slope, (float*)workspace, prepacked, st);
-            g_last_route = 4;
-            NEMAR_CHECK_LAUNCH("conv2d_fwd (7x7 many -> few, 16-bit pipe)");
-            return NEMAR_OK;
+    const char* what = "conv2d_fwd";
+    g_last_route = P.route;
+    switch (P.route) {
+    case ROUTE_K7:
+        if (P.sub == FwdPlan::K7_MANY_FEW) {
+            k7_mf_run(P.k7, x0, w, K, C, 0, bias, y, N, H, W, 0, act, slope, (float*)workspace, prepacked, st);
+            what = "conv2d_fwd (7x7 many -> few, 16-bit pipe)";
+        } else {
+            if (!prepacked) nemar_k7_fm_pack(w, (long long)C * 49, 49, 0, K, C, workspace, st);
+            nemar_k7_fm_conv(x0, C, H, W, 3, pad_mode == BORDER_REFLECT, workspace, bias, y, K, N, H, W, act, slope, 0, st);
+            what = "conv2d_fwd (7x7, 16-bit pipe)";
         }
-    }
-    if (g_k7 && C1 == 0 && act != ACT_TANH && nemar_k7_fm_eligible(C, K, R, S, stride, pad)) {
-        // 7x7 stem (<= 4 input channels): row-expanded source on the 16-bit matrix pipe, weights in registers (conv_k7.hip)
-        if (!prepacked) nemar_k7_fm_pack(w, (long long)C * 49, 49, 0, K, C, workspace, st);
-        nemar_k7_fm_conv(x0, C, H, W, 3, pad_mode == BORDER_REFLECT, workspace, bias, y, K, N, H, W, act, slope, 0, st);
-        g_last_route = 4;
-        NEMAR_CHECK_LAUNCH("conv2d_fwd (7x7, 16-bit pipe)");
-        return NEMAR_OK;
-    }
-    if (nemar_narrow_eligible(K, C1, R, S, stride, N, OH, OW) && g_narrow) {
-        // the narrow kernels read the weights in place: the packed-weight workspace doubles as the slab space of their
-        // channel-split mode (the split count is capped to what fits, see nemar_narrow_fwd)
+        break;
+    case ROUTE_NARROW:
+        // (the weights are read in place: the packed-weight workspace is the slab space of the channel-split mode, see nemar_narrow_fwd)
         nemar_narrow_fwd(x0, w, bias, y, N, C, H, W, K, R, pad, pad_mode, act, slope,
                          g_deterministic ? (float*)workspace : nullptr, ws_bytes / sizeof(float), st);
-        g_last_route = 1;
-        NEMAR_CHECK_LAUNCH("conv2d_fwd (narrow)");
-        return NEMAR_OK;
-    }
-    {
+        what = "conv2d_fwd (narrow)";
+        break;
+    case ROUTE_SPLIT16: {
         const int mode = pad_mode == BORDER_REFLECT ? SPLIT16_REFLECT : SPLIT16_ZERO;
-        if (g_split16 && C1 == 0 && act == ACT_NONE && split16_worth_it(N, OH, OW, K, C, R, S) &&
-            nemar_split16_eligible(N, H, W, K, C, R, S, stride, pad, mode, g_split16_variant) &&
-            call.scratch && call.scratch_bytes >= nemar_split16_scratch_total(N, H, W, K, C, OH, OW)) {
-            if (!prepacked) nemar_split16_pack(w, workspace, K, C, R, 0, g_split16_variant, st);
-            nemar_split16_conv(x0, workspace, bias, y, N, H, W, K, C, R, 1, H, W, OH, OW, mode, call.scratch, g_xcd_map, g_split16_variant,
-                               g_tl, nullptr, call.src_max, call.src_planes, call.src_planes_kind, nullptr, nullptr, st);
-            g_last_route = 2;
-            NEMAR_CHECK_LAUNCH("conv2d_fwd (split-16)");
-            return NEMAR_OK;
+        if (!prepacked) nemar_split16_pack(w, workspace, K, C, R, 0, g_split16_variant, st);
+        nemar_split16_conv(x0, workspace, bias, y, N, H, W, K, C, R, 1, H, W, OH, OW, mode, call.scratch, g_xcd_map, g_split16_variant,
+                           g_tl, nullptr, call.src_max, call.src_planes, call.src_planes_kind, nullptr, nullptr, st);
+        what = "conv2d_fwd (split-16)";
+        break;
+    }
+    case ROUTE_S16G: {
+        S16gProblem& q = P.q;
+        q.src0 = x0; q.src1 = x1; q.dst0 = y; q.dst1 = nullptr; q.bias = bias; q.dbg = g_dbg; q.tl = g_tl;
+        if (!prepacked) nemar_s16g_pack(q, P.pl, w, (long long)C * R * S, (long long)R * S, workspace, st);
+        nemar_s16g_conv(q, P.pl, workspace, st);
+        what = "conv2d_fwd (16-bit pipe, in-kernel split)";
+        break;
+    }
+    default: {
+        IgemmParams p;
+        fwd_taps(p.taps, R, S, pad);
+        if (!prepacked) launch_pack(w, (float*)workspace, K, C, C * R * S, R * S, p.taps, st);
+        p.src0 = x0; p.src1 = x1; p.C0 = C0; p.C1 = C1; p.Hs = H; p.Ws = W;
+        p.wp = (const float*)workspace; p.M = K; p.Mpad = igemm_mpad(K); p.Kred = C * R * S;
+        p.zero = p.wp + packed_core_floats(K, C * R * S);
+        p.dbg = g_dbg; p.tl = g_tl;
+        p.ring_p = 0; p.ring_H = 0; p.ring_W = 0; p.ksplit = 1; p.part = nullptr; p.part_stride = 0;
+        p.rf = 0; p.rf_row = nullptr; p.rf_col = nullptr; p.xcd = 0;
+        p.bias = bias;
+        p.dst0 = y; p.dst1 = nullptr; p.M0 = K;
+        p.OH = OH; p.OW = OW; p.OHf = OH; p.OWf = OW; p.osy = 1; p.ooy = 0; p.osx = 1; p.oox = 0;
+        p.N = N; p.P = N * OH * OW;
+        p.sy = stride; p.sx = stride; p.border = pad_mode; p.act = act; p.slope = slope; p.pad = pad;
+        p.fd_ohw = make_fastdiv(OH * OW); p.fd_ow = make_fastdiv(OW); p.fd_cs = make_fastdiv(C);
+        if (P.sub != FwdPlan::PLAIN) {      // slab 0 carries the bias; an activation follows the sum (ReLU / LeakyReLU)
+            p.ksplit = P.ksplit;
+            p.part = (float*)workspace + P.slab_off;
+            p.part_stride = (long long)N * K * OH * OW;
+            p.act = ACT_NONE;
         }
+        launch_igemm(p, st);
+        if (P.sub == FwdPlan::SPLIT_ACT) nemar_sum_partials_act(p.part, p.part_stride, p.ksplit, y, p.part_stride, act == ACT_RELU ? 1 : 2, slope, st);
+        else if (P.sub == FwdPlan::SPLIT) nemar_sum_partials(p.part, p.part_stride, p.ksplit, y, p.part_stride, false, st);
     }
-    {
-        S16gProblem q;
-        S16gPlan pl;
-        if (s16g_fwd_problem(q, pl, N, C0, C1, H, W, K, R, S, stride, pad, pad_mode, act, slope)) {
-            q.src0 = x0; q.src1 = x1; q.dst0 = y; q.dst1 = nullptr; q.bias = bias; q.dbg = g_dbg; q.tl = g_tl;
-            if (!prepacked) nemar_s16g_pack(q, pl, w, (long long)C * R * S, (long long)R * S, workspace, st);
-            nemar_s16g_conv(q, pl, workspace, st);
-            g_last_route = 3;
-            NEMAR_CHECK_LAUNCH("conv2d_fwd (16-bit pipe, in-kernel split)");
-            return NEMAR_OK;
-        }
     }
-    IgemmParams p;
-    fwd_taps(p.taps, R, S, pad);
-    if (!prepacked) launch_pack(w, (float*)workspace, K, C, C * R * S, R * S, p.taps, st);
-    p.src0 = x0; p.src1 = x1; p.C0 = C0; p.C1 = C1; p.Hs = H; p.Ws = W;
-    p.wp = (const float*)workspace; p.M = K; p.Mpad = igemm_mpad(K); p.Kred = C * R * S;
-    p.zero = p.wp + packed_core_floats(K, C * R * S);
-    p.dbg = g_dbg; p.tl = g_tl;
-    p.ring_p = 0; p.ring_H = 0; p.ring_W = 0; p.ksplit = 1; p.part = nullptr; p.part_stride = 0;
-    p.rf = 0; p.rf_row = nullptr; p.rf_col = nullptr; p.xcd = 0;
-    p.bias = bias;
-    p.dst0 = y; p.dst1 = nullptr; p.M0 = K;
-    p.OH = OH; p.OW = OW; p.OHf = OH; p.OWf = OW; p.osy = 1; p.ooy = 0; p.osx = 1; p.oox = 0;
-    p.N = N; p.P = N * OH * OW;
-    p.sy = stride; p.sx = stride; p.border = pad_mode; p.act = act; p.slope = slope; p.pad = pad;
-    p.fd_ohw = make_fastdiv(OH * OW); p.fd_ow = make_fastdiv(OW); p.fd_cs = make_fastdiv(C);
-    // A layer with a fused ReLU / LeakyReLU splits too: the activation is applied by the sum pass (nemar_sum_partials_act).  The registration
-    // net's decoder and first-of-level layers at <= 16 x 16 (72 .. 144 serial stages in one or two workgroups: 33 / 57 us per call) take
-    // ~10 us + the sum; same-box A/B 27.41 -> 27.07 ms per step (profiles/r6_d_wgrad_lane_and_split_act_ab.txt).  nemar_tune(36, 0): off.
-    const bool split_act = g_split_act && (act == ACT_RELU || act == ACT_LRELU);
-    if (FL.ksplit > 1 && (act == ACT_NONE || split_act)) {      // slab 0 carries the bias; an activation follows the sum (ReLU / LeakyReLU)
-        p.ksplit = FL.ksplit;
-        p.part = (float*)workspace + FL.slab_off;
-        p.part_stride = (long long)N * K * OH * OW;
-        p.act = ACT_NONE;
-    }
-    launch_igemm(p, st);
-    if (p.ksplit > 1) {
-        if (split_act) nemar_sum_partials_act(p.part, p.part_stride, p.ksplit, y, p.part_stride, act == ACT_RELU ? 1 : 2, slope, st);
-        else nemar_sum_partials(p.part, p.part_stride, p.ksplit, y, p.part_stride, false, st);
-    }
-    g_last_route = 0;
-    NEMAR_CHECK_LAUNCH("conv2d_fwd");
+    NEMAR_CHECK_LAUNCH(what);
     return NEMAR_OK;
 }
 
 // Data gradient of the conv above: gy [N,K,OH,OW] -> gx [N,C,H,W] (split over gx0[C0] | gx1[C1]; gx0 may be NULL to
 // skip its channels).  With bias/act it is also the FORWARD of nn.ConvTranspose2d(K -> C) whose weight is w[K][C][R][S].
-NEMAR_API size_t nemar_conv2d_bwd_data_workspace(int N, int C, int H, int W, int K, int R, int S, int stride, int pad,
-                                                 int pad_mode) {
+NEMAR_API size_t nemar_conv2d_bwd_data_workspace(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
     if (N <= 0 || C <= 0 || K <= 0 || R <= 0 || S <= 0 || stride < 1) return 0;
-    return sizeof(float) * dgrad_layout(N, C, H, W, K, R, S, stride, pad, pad_mode).total;
+    return sizeof(float) * plan_dgrad({N, C, 0, H, W, K, R, S, stride, pad, pad_mode}, ConvFacts::canonical()).total;
 }
 
 // Honours call.scratch, .src_max, .src_planes, .gy_planes_out, .addend and .out_max; sets .gy_planes_written, .epilogue_fused, .addend_done
@@ -985,116 +669,73 @@ static int conv2d_bwd_data(ConvCall& call, const float* gy, const float* w, cons
     NEMAR_REQUIRE(!refl || (!bias && act == ACT_NONE && gx1 == nullptr),
                   "conv2d_bwd_data: reflect mode supports a single destination without bias/activation");
     NEMAR_REQUIRE(!refl || stride > 1 || pad <= 4, "conv2d_bwd_data: reflect pad %d > 4 unsupported", pad);
-    const DgradLayout L = dgrad_layout(N, C, H, W, K, R, S, stride, pad, pad_mode);
+    ConvFacts f = facts_of(call, bias, act, slope);
+    f.gx0 = gx0 != nullptr; f.gx1 = gx1 != nullptr;
+    f.gy_planes_bytes = call.gy_planes_out ? call.gy_planes_bytes : 0;
+    DgradPlan L = plan_dgrad({N, C0, C1, H, W, K, R, S, stride, pad, pad_mode}, f);
     if (ws_bytes < sizeof(float) * L.total) {
         nemar_set_error("conv2d_bwd_data: workspace %zu < %zu", ws_bytes, sizeof(float) * L.total);
         return NEMAR_EWORKSPACE;
     }
-    NEMAR_REQUIRE((long long)N * (H + 2 * pad) * (W + 2 * pad) < (1ll << 31) && (long long)K * OH * OW < (1ll << 31) &&
-                      (long long)K * R * S < (1 << 20),
+    NEMAR_REQUIRE((long long)N * (H + 2 * pad) * (W + 2 * pad) < (1ll << 31) && (long long)K * OH * OW < (1ll << 31) && (long long)K * R * S < (1 << 20),
                   "conv2d_bwd_data: problem too large for 32-bit tile indexing");
     hipStream_t st = (hipStream_t)stream;
     float* wsf = (float*)workspace;
-    if (C1 == 0 && gx0 && !bias && act == ACT_NONE && k7_mf_eligible(K, C, R, S, stride, pad)) {
-        // 7x7 stem (<= 4 input channels): gx = the many -> few correlation of gy with flipped, transposed weights; reflect border: on the
-        // padded domain (gy through a 6-texel zero border), folded back inside the shift-sum pass
-        const K7MfPlan m = k7_mf_plan(N, K, OH, OW, refl ? 6 : 3, BORDER_ZERO);
-        if (m.ok) {
-            k7_mf_run(m, gy, w, C, K, 1, nullptr, gx0, N, H, W, refl ? 1 : 0, ACT_NONE, 0.f, wsf, prepacked, st);
-            g_last_route = 4;
-            NEMAR_CHECK_LAUNCH("conv2d_bwd_data (7x7 many -> few, 16-bit pipe)");
-            return NEMAR_OK;
-        }
-    }
-    if (g_k7 && C1 == 0 && gx0 && !bias && act == ACT_NONE && C > 4 && nemar_k7_fm_eligible(K, C, R, S, stride, pad)) {
-        // 7x7 head (<= 4 output channels): the data gradient is a few -> many convolution of gy with flipped, transposed weights
-        // (conv_k7.hip).  Reflect border: on the padded (H + 6) x (W + 6) domain (gy through a 6-texel zero border), then the fold.
+    const long long total = (long long)N * C * H * W;
+    const int mskip = L.mskip;        // skipping the first C0 channels when gx0 == NULL: start the M range at C0
+    const char* what = "conv2d_bwd_data";
+    g_last_route = L.route;
+    switch (L.sub) {
+    case DgradPlan::K7_MANY_FEW:
+        k7_mf_run(L.k7, gy, w, C, K, 1, nullptr, gx0, N, H, W, L.k7_fold, ACT_NONE, 0.f, wsf, prepacked, st);
+        what = "conv2d_bwd_data (7x7 many -> few, 16-bit pipe)";
+        break;
+    case DgradPlan::K7_FEW_MANY:
         if (!prepacked) nemar_k7_fm_pack(w, 49, (long long)C * 49, 1, C, K, workspace, st);
-        if (refl && nemar_k7_fm_fold_ok(H, W)) {             // mirrored contributions accumulated in the kernel: no padded tensor, no fold pass
-            nemar_k7_fm_conv(gy, K, OH, OW, 6, 0, workspace, nullptr, gx0, C, N, H, W, ACT_NONE, 0.f, 1, st);
-        } else if (refl) {
+        if (L.k7_fold == 2) {             // reflect: on the padded (H + 6) x (W + 6) domain (gy through a 6-texel zero border), then the fold
             float* padded = wsf + ((nemar_k7_fm_pack_floats(C) + 3) & ~(size_t)3);
             nemar_k7_fm_conv(gy, K, OH, OW, 6, 0, workspace, nullptr, padded, C, N, H + 6, W + 6, ACT_NONE, 0.f, 0, st);
-            const long long total = (long long)N * C * H * W;
-            hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, (const float*)padded, gx0, H, W, pad,
-                               total, (const float*)nullptr);
-        } else {
-            nemar_k7_fm_conv(gy, K, OH, OW, 3, 0, workspace, nullptr, gx0, C, N, H, W, ACT_NONE, 0.f, 0, st);
+            fold_padded(padded, gx0, H, W, pad, total, nullptr, st);
+        } else {                          // (k7_fold == 1: mirrored contributions accumulated in the kernel: no padded tensor, no fold pass)
+            nemar_k7_fm_conv(gy, K, OH, OW, L.k7_fold ? 6 : 3, 0, workspace, nullptr, gx0, C, N, H, W, ACT_NONE, 0.f, L.k7_fold, st);
         }
-        g_last_route = 4;
-        NEMAR_CHECK_LAUNCH("conv2d_bwd_data (7x7, 16-bit pipe)");
-        return NEMAR_OK;
+        what = "conv2d_bwd_data (7x7, 16-bit pipe)";
+        break;
+    case DgradPlan::SPLIT16: {
+        if (!prepacked) nemar_split16_pack(w, workspace, K, C, R, 1, g_split16_variant, st);
+        const Split16Done done = nemar_split16_conv(gy, workspace, nullptr, gx0, N, H, W, C, K, R, R - 1 - pad, OH, OW, H, W,
+                                                    refl ? SPLIT16_DGRAD_REFLECT : SPLIT16_ZERO, call.scratch, g_xcd_map, g_split16_variant, g_tl,
+                                                    L.want_gy_planes ? call.gy_planes_out : nullptr, call.src_max, call.src_planes,
+                                                    call.src_planes_kind, call.addend, call.out_max, st);
+        call.gy_planes_written = done.dual_written;
+        call.epilogue_fused = done.epilogue_fused;
+        what = "conv2d_bwd_data (split-16)";
+        break;
     }
-    {
-        // 3x3 stride-1 layers: the data gradient is the same convolution with flipped, transposed weights (conv_split16.hip)
-        const int mode = refl ? SPLIT16_DGRAD_REFLECT : SPLIT16_ZERO;
-        if (g_split16 && C1 == 0 && gx0 && !bias && act == ACT_NONE && split16_worth_it(N, OH, OW, K, C, R, S) &&
-            nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, mode, g_split16_variant) &&
-            call.scratch && call.scratch_bytes >= nemar_split16_scratch_total(N, H, W, C, K, H, W)) {
-            if (!prepacked) nemar_split16_pack(w, workspace, K, C, R, 1, g_split16_variant, st);
-            void* dual = nullptr;      // the weight gradient of the same layer follows and takes its gy planes from this call's split pass
-            if (g_dual_gy && R == 3 && call.gy_planes_out && call.gy_planes_bytes >= nemar_split16_wgrad_g_bytes(N, H, W, K, R) &&
-                nemar_split16_wgrad_g_bytes(N, H, W, K, R) > 0 && nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad))
-                dual = call.gy_planes_out;
-            // (whether the planes were written is the split pass's own decision: variant, producer planes, g_dual_gy — ask it)
-            const Split16Done done = nemar_split16_conv(gy, workspace, nullptr, gx0, N, H, W, C, K, R, R - 1 - pad, OH, OW, H, W, mode, call.scratch,
-                                                        g_xcd_map, g_split16_variant, g_tl, dual, call.src_max, call.src_planes,
-                                                        call.src_planes_kind, call.addend, call.out_max, st);
-            call.gy_planes_written = done.dual_written;
-            call.epilogue_fused = done.epilogue_fused;
-            g_last_route = 2;
-            NEMAR_CHECK_LAUNCH("conv2d_bwd_data (split-16)");
-            return NEMAR_OK;
-        }
+    case DgradPlan::S16G:
+    case DgradPlan::S16G_FOLD: {            // (fold: one destination, no skip — the gradient of the padded input into scratch, then the fold)
+        const bool fold16 = L.sub == DgradPlan::S16G_FOLD;
+        S16gProblem& q = L.q;
+        q.src0 = gy; q.src1 = nullptr; q.bias = bias ? bias + mskip : nullptr;
+        if (fold16) { q.dst0 = wsf + L.padded_off; q.dst1 = nullptr; q.M0 = q.M; }
+        else if (mskip) { q.dst0 = gx1; q.dst1 = nullptr; q.M0 = q.M; }
+        else { q.dst0 = gx0; q.dst1 = gx1; q.M0 = C0; }
+        // output row m = input channel m + mskip, reduction channel = k:  w[k][c][r][s]
+        if (!prepacked) nemar_s16g_pack(q, L.pl, w + (size_t)mskip * R * S, (long long)R * S, (long long)C * R * S, workspace, st);
+        nemar_s16g_conv(q, L.pl, workspace, st);
+        if (fold16) fold_padded(q.dst0, gx0, H, W, pad, total, call.addend, st);
+        if (fold16 && call.addend) call.addend_done = true;
+        what = fold16 ? "conv2d_bwd_data (16-bit pipe on the padded domain + fold)" : "conv2d_bwd_data (16-bit pipe, in-kernel split)";
+        break;
     }
-    if (!refl) {
-        const int mskip0 = (gx0 == nullptr) ? C0 : 0;
-        S16gProblem q;
-        S16gPlan pl;
-        if (s16g_dgrad_problem(q, pl, N, C, mskip0, H, W, K, OH, OW, R, S, stride, pad, act, slope)) {
-            q.src0 = gy; q.src1 = nullptr; q.bias = bias ? bias + mskip0 : nullptr;
-            if (mskip0) { q.dst0 = gx1; q.dst1 = nullptr; q.M0 = q.M; }
-            else { q.dst0 = gx0; q.dst1 = gx1; q.M0 = C0; }
-            // output row m = input channel m + mskip0, reduction channel = k:  w[k][c][r][s]
-            if (!prepacked) nemar_s16g_pack(q, pl, w + (size_t)mskip0 * R * S, (long long)R * S, (long long)C * R * S, workspace, st);
-            nemar_s16g_conv(q, pl, workspace, st);
-            g_last_route = 3;
-            NEMAR_CHECK_LAUNCH("conv2d_bwd_data (16-bit pipe, in-kernel split)");
-            return NEMAR_OK;
-        }
-    }
-    if (refl && L.fold16 && gx1 == nullptr && gx0 && !bias && act == ACT_NONE) {
-        S16gProblem q;
-        S16gPlan pl;
-        const int Hp = H + 2 * pad, Wp = W + 2 * pad;
-        if (s16g_dgrad_problem(q, pl, N, C, 0, Hp, Wp, K, OH, OW, R, S, 1, 0, ACT_NONE, 0.f)) {
-            float* const padded16 = wsf + L.padded_off;
-            q.src0 = gy; q.src1 = nullptr; q.bias = nullptr; q.dst0 = padded16; q.dst1 = nullptr; q.M0 = q.M;
-            if (!prepacked) nemar_s16g_pack(q, pl, w, (long long)R * S, (long long)C * R * S, workspace, st);
-            nemar_s16g_conv(q, pl, workspace, st);
-            const long long total = (long long)N * C * H * W;
-            hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, (const float*)padded16, gx0, H,
-                               W, pad, total, call.addend);
-            if (call.addend) call.addend_done = true;
-            g_last_route = 3;
-            NEMAR_CHECK_LAUNCH("conv2d_bwd_data (16-bit pipe on the padded domain + fold)");
-            return NEMAR_OK;
-        }
-    }
-    const size_t pack_stride = L.pack_stride;
-    // Reflect padding.  The gradient w.r.t. the PADDED input splits into the image interior — exactly the zero-padded
-    // data gradient, computed on the unpadded domain — and the border ring, whose texels are mirrors of in-image
-    // texels: a second, small launch evaluates the same implicit GEMM at the ring positions only into a compact scratch,
-    // and ring_gather_kernel adds each ring texel to the texel it mirrors (stride 1; gather form, no atomics).  Strided
-    // reflect convolutions (not on the hot path) keep the simple form: differentiate on the padded domain into
-    // scratch, then fold.
+    case DgradPlan::EXACT: {
+    // Reflect padding, ring form: the zero-padded data gradient on the unpadded domain, then the same implicit GEMM at the border-ring positions
+    // into a compact scratch, which ring_gather_kernel adds to the texels it mirrors.  Fold form: the padded domain into scratch, then the fold.
     const bool ring = L.ring, fold = L.fold;
     bool folded = false;                  // fold_small: the slab sum folded the border already
     const int Hd = fold ? H + 2 * pad : H, Wd = fold ? W + 2 * pad : W;
     const int padd = fold ? 0 : pad;
     float* padded = fold ? wsf + L.padded_off : nullptr;
-    // skipping the first C0 channels when gx0 == NULL: start the M range at C0
-    const int mskip = (gx0 == nullptr) ? C0 : 0;
     int cls = 0;
     for (int ph = 0; ph < stride; ++ph)
         for (int pw = 0; pw < stride; ++pw, ++cls) {
@@ -1116,7 +757,7 @@ static int conv2d_bwd_data(ConvCall& call, const float* gy, const float* w, cons
             p.ring_p = 0; p.ring_H = 0; p.ring_W = 0; p.ksplit = 1; p.part = nullptr; p.part_stride = 0;
             p.rf = 0; p.rf_row = nullptr; p.rf_col = nullptr; p.xcd = 0;
             p.fd_ohw = make_fastdiv(OHc * OWc); p.fd_ow = make_fastdiv(OWc); p.fd_cs = make_fastdiv(K);
-            float* wp = wsf + pack_stride * (size_t)cls;
+            float* wp = wsf + L.pack_stride * (size_t)cls;
             p.wp = wp;
             p.zero = wp + packed_core_floats(Mc, K * (p.taps.n > 0 ? p.taps.n : 1));
             p.dbg = g_dbg; p.tl = nullptr;
@@ -1127,12 +768,9 @@ static int conv2d_bwd_data(ConvCall& call, const float* gy, const float* w, cons
             }
             // A[(t*K + k)][c] = w[k][c + mskip][r][s]
             if (!prepacked) launch_pack(w + (size_t)mskip * R * S, wp, Mc, K, R * S, C * R * S, p.taps, st);
-            // <= 4 input channels (the translation net's stem: 29 of 32 MFMA rows would be empty): the zero-padded
-            // data gradient is a <= 4-output-channel correlation of gy — the narrow VALU kernel's job
-            const bool narrow = g_narrow && stride == 1 && !fold && !bias && act == ACT_NONE && mskip == 0 && gx1 == nullptr &&
-                                R - 1 - pad >= 0 && nemar_narrow_eligible(C, 0, R, S, 1, N, H, W);
             bool ring_done = false;
-            if (narrow) {
+            if (L.narrow) {
+                // <= 4 input channels: the zero-padded data gradient is a <= 4-output-channel correlation of gy — the narrow VALU kernel's job
                 float* w2 = wsf + L.w2_off;
                 if (!prepacked) {
                     if (nemar_pack_recording()) {
@@ -1144,26 +782,23 @@ static int conv2d_bwd_data(ConvCall& call, const float* gy, const float* w, cons
                 }
                 nemar_narrow_fwd(gy, w2, nullptr, gx0, N, K, OH, OW, C, R, R - 1 - pad, BORDER_ZERO, ACT_NONE, 0.f, nullptr, 0, st);
             } else {
-                // split reductions (see dgrad_layout): each split stores its partial gradient to its own slab, summed in order
-                if (L.ksplit > 1 && !bias && act == ACT_NONE && mskip == 0 && (fold ? (gx0 != nullptr && gx1 == nullptr) : (gx1 == nullptr || (gx0 != nullptr && !ring)))) {
+                if (L.split) {      // each split stores its partial gradient to its own slab, summed in order
                     p.ksplit = L.ksplit;
                     p.part = wsf + L.slab_off;
                     p.part_stride = (long long)N * C * Hd * Wd;       // (fold_small: slabs of the padded domain)
                     if (gx1) { p.M0 = C; p.dst1 = nullptr; }      // two destinations: the slabs hold all C rows, the sum pass parts them
                 }
-                // 3x3 reflect layers that run on the wave-specialised 16-byte-load kernel fold the border INTO the main launch
-                // (reflect_aux_kernel); everything else adds the border ring with a second launch below
+                // on the wave-specialised 16-byte-load kernel the border folds INTO the main launch (reflect_aux_kernel); else the ring launch below
                 bool vec = false;
-                if (ring && g_reflect_aux && pad == 1 && R == 3 && S == 3 && H >= 4 && W >= 8 && route_ws2(p, &vec) && vec) {
-                    float* rows = wsf + L.aux_rows_off;
-                    float* cols = wsf + L.aux_cols_off;
+                if (L.aux_rows && route_ws2(p, &vec) && vec) {
+                    float* rows = wsf + L.aux_rows_off, * cols = wsf + L.aux_cols_off;
                     hipLaunchKernelGGL(reflect_aux_kernel, dim3(nemar_stream_grid(6ll * N * K * W + 8ll * N * K * H, 256)),
                                        dim3(256), 0, st, gy, rows, cols, N, K, H, W);
                     p.rf = 1; p.rf_row = rows; p.rf_col = cols;
                     ring_done = true;
                 }
                 launch_igemm(p, st);
-                if (p.ksplit > 1 && fold) {                       // slabs of the padded domain -> sum + fold in one pass (gx1 == nullptr: checked above)
+                if (p.ksplit > 1 && fold) {                       // slabs of the padded domain -> sum + fold in one pass (one destination: the plan)
                     nemar_sum_partials_fold(p.part, p.part_stride, p.ksplit, gx0, (long long)N * C, H, W, pad, call.addend, st);
                     if (call.addend) call.addend_done = true;
                     folded = true;
@@ -1200,97 +835,23 @@ static int conv2d_bwd_data(ConvCall& call, const float* gy, const float* w, cons
             }
         }
     if (fold && !folded) {
-        const long long total = (long long)N * C * H * W;
         const float* const add = (gx0 && !gx1) ? call.addend : nullptr;
-        hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st,
-                           (const float*)padded, gx0 ? gx0 : gx1, H, W, pad, total, add);
+        fold_padded(padded, gx0 ? gx0 : gx1, H, W, pad, total, add, st);
         if (add) call.addend_done = true;
     }
-    g_last_route = 0;
-    NEMAR_CHECK_LAUNCH("conv2d_bwd_data");
+    }
+    }
+    NEMAR_CHECK_LAUNCH(what);
     return NEMAR_OK;
 }
 
-// ---- weight gradient ------------------------------------------------------------------------------------------------
-namespace {
-void legacy_wgrad_plan(int K, int J, int P, int* splits_out, int* pix_per_split_out) {
-    const bool wide = K > 32;
-    const int BM = wide ? 128 : 32, BN = wide ? 128 : 256;
-    const int mt = nemar_cdiv(K, BM), jt = nemar_cdiv(J, BN);
-    // split the pixel reduction so that ~4 workgroups per CU exist, but keep >= 8 stages per split
-    int splits = nemar_cdiv(1024, mt * jt);
-    const int max_splits = nemar_cdiv(P, WBK * 8);
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (splits > 65535) splits = 65535;
-    *pix_per_split_out = nemar_cdiv(nemar_cdiv(P, splits), WBK) * WBK;
-    *splits_out = nemar_cdiv(P, *pix_per_split_out);
-}
-constexpr int BIAS_CHUNK = 4096;
-
-// Layers whose gy planes are not a multiple of 4 floats (the discriminator's 31x31 / 15x15 maps) cannot be read in aligned
-// 16-byte chunks; instead of the first-generation VGPR-staged kernel (62 TF on the 256->512 k4 layer) gy is copied once into
-// planes of OHv >= OH rows with (OHv * OW) % 4 == 0, zero-filled below row OH, and the wave-specialised kernel runs on the
-// virtual OHv x OW map: the extra rows multiply whatever source texel they address by zero.
-int padded_rows(int OH, int OW) {
-    int ohv = OH;
-    while ((ohv * OW) % 4) ++ohv;
-    return ohv;
-}
-__global__ __launch_bounds__(256) void pad_planes_kernel(const float* __restrict__ src, float* __restrict__ dst, int plane,
-                                                         int plane_padded, long long total) {
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const long long pl = idx / plane_padded;
-        const int r = (int)(idx - pl * plane_padded);
-        dst[idx] = r < plane ? src[pl * plane + r] : 0.f;
-    }
-}
-bool wgrad_pad_route(int K, int OH, int OW, int pad_mode) {
-    return K > 4 && (OH * OW) % 4 != 0 && pad_mode == BORDER_ZERO && g_wgrad != 1;
-}
-}  // namespace
-
-// Scratch of the weight / bias gradient: per-split slabs of the fixed-order reduction (max over the kernels the shape can
-// be routed to; the routing also depends on the alignment of gy, unknown here).
-NEMAR_API size_t nemar_conv2d_bwd_weight_workspace(int N, int C, int H, int W, int K, int OH, int OW, int R, int S,
-                                                   int stride, int pad) {
+// ---- weight gradient.  Its scratch: per-split slabs of the fixed-order reduction (max over the routes the shape could take) ----
+NEMAR_API size_t nemar_conv2d_bwd_weight_workspace(int N, int C, int H, int W, int K, int OH, int OW, int R, int S, int stride, int pad) {
     if (N <= 0 || C <= 0 || K <= 0 || OH <= 0 || OW <= 0 || R <= 0 || S <= 0) return 0;
-    const int J = C * R * S, P = N * OH * OW;
-    size_t fl = 0;
-    int splits, pps;
-    nemar_wgrad2_plan(K, J, P, g_wgrad_blocks, &splits, &pps);
-    fl = (size_t)splits * ((size_t)K * J + K);
-    legacy_wgrad_plan(K, J, P, &splits, &pps);
-    const size_t f2 = (size_t)splits * ((size_t)K * J + K);
-    if (f2 > fl) fl = f2;
-    if ((OH * OW) % 4 != 0 && K > 4) {          // padded-gy route: slabs of the virtual map + the padded copy of gy
-        const int ohv = padded_rows(OH, OW);
-        nemar_wgrad2_plan(K, J, N * ohv * OW, g_wgrad_blocks, &splits, &pps);
-        const size_t f4 = (size_t)splits * ((size_t)K * J + K) + 4 + (size_t)N * K * ohv * OW;
-        if (f4 > fl) fl = f4;
-    }
-    if (K <= 4) {
-        const size_t f3 = (size_t)nemar_narrow_wgrad_splits(N, C, OH, OW) * K * J + (size_t)N * nemar_cdiv(OH * OW, BIAS_CHUNK) * K;
-        if (f3 > fl) fl = f3;
-    }
-    if (nemar_s16g_wgrad_eligible(N, C, 0, H, W, K, OH, OW, R, S, stride, pad, BORDER_ZERO)) {      // (slab count: same for any channel split)
-        const size_t f6 = (size_t)nemar_s16g_wgrad_slabs_max(N, C, K, OH, W, stride) * ((size_t)K * J + K);
-        if (f6 > fl) fl = f6;
-    }
-    if (nemar_k7_wgrad_eligible(N, C, H, W, K, R, S, stride, pad)) {            // 7x7 stem / head: slabs + max words + bias partials
-        const size_t f7 = nemar_k7_wgrad_floats(N, C, H, W, K) + (size_t)N * nemar_cdiv(OH * OW, BIAS_CHUNK) * K;
-        if (f7 > fl) fl = f7;
-    }
-    if (nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad)) {       // slabs of the split-16 route + bias partials
-        const size_t f5 = (size_t)nemar_split16_wgrad_splits(N, C, H, W, K, R) * K * J + (size_t)N * nemar_cdiv(OH * OW, BIAS_CHUNK) * K;
-        if (f5 > fl) fl = f5;
-    }
-    return sizeof(float) * fl;
+    return sizeof(float) * plan_wgrad({N, C, 0, H, W, K, R, S, stride, pad, BORDER_ZERO, OH, OW}, ConvFacts::canonical()).total;
 }
 
-// gw[K][C][R][S] += d loss / d w, and (gb != NULL) gb[K] += sum_pixels gy   (always accumulate: the caller
-// zero-fills once per optimizer step)
+// gw[K][C][R][S] += d loss / d w, and (gb != NULL) gb[K] += sum_pixels gy   (always accumulate: the caller zero-fills once per optimizer step)
 // Honours call.scratch, .src_max (x0), .src2_max (gy), .x_planes, .src2_planes and .bias_partials (the wide route); sets .bias_rode
 static int conv2d_bwd_weight(ConvCall& call, const float* x0, int C0, const float* x1, int C1, const float* gy, float* gw,
                              float* gb, int N, int H, int W, int K, int OH, int OW, int R, int S, int stride,
@@ -1302,9 +863,14 @@ static int conv2d_bwd_weight(ConvCall& call, const float* x0, int C0, const floa
     NEMAR_REQUIRE(pad_mode == BORDER_ZERO || (pad < H && pad < W), "conv2d_bwd_weight: reflect pad too large");
     NEMAR_REQUIRE((long long)N * OH * OW < (1ll << 31) && (long long)(C0 + C1) * H * W < (1ll << 31),
                   "conv2d_bwd_weight: problem too large for 32-bit tile indexing");
+    ConvFacts f = facts_of(call, nullptr, ACT_NONE, 0.f);
+    f.part = g_deterministic != 0;
+    f.gy_aligned = (reinterpret_cast<uintptr_t>(gy) & 15) == 0;
+    f.part_aligned = (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
+    const WgradPlan P = plan_wgrad({N, C0, C1, H, W, K, R, S, stride, pad, pad_mode, OH, OW}, f);
     float* part = nullptr;
     if (g_deterministic) {
-        const size_t need = nemar_conv2d_bwd_weight_workspace(N, C0 + C1, H, W, K, OH, OW, R, S, stride, pad);
+        const size_t need = sizeof(float) * P.total;
         if (!workspace || ws_bytes < need) {
             nemar_set_error("conv2d_bwd_weight: workspace %zu < %zu", workspace ? ws_bytes : (size_t)0, need);
             return NEMAR_EWORKSPACE;
@@ -1313,105 +879,64 @@ static int conv2d_bwd_weight(ConvCall& call, const float* x0, int C0, const floa
     }
     hipStream_t st = (hipStream_t)stream;
     const int J = (C0 + C1) * R * S;
-    if (g_k7 && part && C1 == 0 && nemar_k7_wgrad_eligible(N, C0, H, W, K, R, S, stride, pad)) {
-        // 7x7 stem / head (<= 4 channels on one side): reduction over pixels on the 16-bit matrix pipe (conv_k7.hip)
-        if (!nemar_k7_wgrad(x0, gy, gw, gb, N, C0, H, W, K, pad_mode, part, st)) {      // (head: K <= 4 planes of gy, its own small reduction)
-            const int chunks = nemar_cdiv(OH * OW, BIAS_CHUNK);
-            float* pb = part + nemar_k7_wgrad_floats(N, C0, H, W, K);
-            hipLaunchKernelGGL(bias_grad_kernel, dim3(K, N, chunks), dim3(256), 0, st, gy, pb, N, K, OH * OW, BIAS_CHUNK);
-            nemar_sum_partials(pb, K, N * chunks, gb, K, true, st);
-        }
-        g_last_route = 4;
-        NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (7x7, 16-bit pipe)");
-        return NEMAR_OK;
-    }
-    if (nemar_narrow_eligible(K, C1, R, S, stride, N, OH, OW) && g_narrow) {
+    const char* what = "conv2d_bwd_weight";
+    g_last_route = P.route;
+    switch (P.sub) {
+    case WgradPlan::K7:
+        if (!nemar_k7_wgrad(x0, gy, gw, gb, N, C0, H, W, K, pad_mode, part, st))      // (head: K <= 4 planes of gy, its own small reduction)
+            bias_grad_slabs(gy, gb, part + P.bias_off, N, K, OH * OW, st);
+        what = "conv2d_bwd_weight (7x7, 16-bit pipe)";
+        break;
+    case WgradPlan::NARROW:
         nemar_narrow_wgrad(x0, gy, gw, N, C0, H, W, K, R, pad, pad_mode, part, st);
-        if (gb) {
-            const int chunks = nemar_cdiv(OH * OW, BIAS_CHUNK);
-            float* pb = part ? part + (size_t)nemar_narrow_wgrad_splits(N, C0, OH, OW) * K * J : nullptr;
-            if (pb) {
-                hipLaunchKernelGGL(bias_grad_kernel, dim3(K, N, chunks), dim3(256), 0, st, gy, pb, N, K, OH * OW, BIAS_CHUNK);
-                nemar_sum_partials(pb, K, N * chunks, gb, K, true, st);
-            } else {
-                hipLaunchKernelGGL(bias_grad_atomic_kernel, dim3(K, N, chunks), dim3(256), 0, st, gy, gb, N, K, OH * OW, BIAS_CHUNK);
-            }
-        }
-        g_last_route = 1;
-        NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (narrow)");
-        return NEMAR_OK;
-    }
-    const bool s16g_wg = g_s16g_wgrad && part && s16g_worth_it((long long)N * OH * OW * K * (C0 + C1) * R * S) &&
-        nemar_s16g_wgrad_eligible(N, C0, C1, H, W, K, OH, OW, R, S, stride, pad, pad_mode);
-    const bool split16_wg = g_split16 && g_split16_variant == 4 && part && C1 == 0 && split16_worth_it(N, OH, OW, K, C0, R, S) &&
-        nemar_split16_wgrad_eligible(N, C0, H, W, K, R, S, stride, pad) &&
-        (R == 3 || pad_mode == BORDER_ZERO) && call.scratch && call.scratch_bytes >= nemar_split16_wgrad_scratch_bytes(N, C0, H, W, K, R);
-    if (s16g_wg && (g_s16g_wgrad_first || !split16_wg)) {
+        if (gb) bias_grad_slabs(gy, gb, part ? part + P.bias_off : nullptr, N, K, OH * OW, st);
+        what = "conv2d_bwd_weight (narrow)";
+        break;
+    case WgradPlan::S16G:
         nemar_s16g_wgrad(x0, C0, x1, C1, gy, gw, gb, N, H, W, K, OH, OW, R, stride, pad_mode, part, g_dbg, st);
-        g_last_route = 3;
-        NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (16-bit pipe, in-kernel split)");
-        return NEMAR_OK;
-    }
-    if (split16_wg) {
-        // wide 3x3 stride-1 layers: fp16 x 3 on the 16-bit matrix pipe (conv_split16_wgrad.hip); bias gradient as its own reduction
+        what = "conv2d_bwd_weight (16-bit pipe, in-kernel split)";
+        break;
+    case WgradPlan::SPLIT16:
         call.bias_rode = gb && call.bias_partials;               // the producer's per-plane sums: reduced inside the slab-sum launch
         nemar_split16_wgrad(x0, gy, gw, N, C0, H, W, K, R, pad_mode == BORDER_REFLECT ? 1 : 0, call.scratch, part, g_xcd_map,
                             R == 3 ? call.src2_planes : nullptr, (R == 3 && pad_mode == BORDER_REFLECT) ? call.x_planes : nullptr,
                             call.src_max, call.src2_max, call.bias_rode ? call.bias_partials : nullptr, gb, st);
-        if (gb && !call.bias_rode) {
-            const int chunks = nemar_cdiv(OH * OW, BIAS_CHUNK);
-            float* pb = part + (size_t)nemar_split16_wgrad_splits(N, C0, H, W, K, R) * K * J;
-            hipLaunchKernelGGL(bias_grad_kernel, dim3(K, N, chunks), dim3(256), 0, st, gy, pb, N, K, OH * OW, BIAS_CHUNK);
-            nemar_sum_partials(pb, K, N * chunks, gb, K, true, st);
-        }
-        g_last_route = 2;
-        NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (split-16)");
-        return NEMAR_OK;
-    }
-    if (g_wgrad != 1 && nemar_wgrad2_eligible(K, OH, OW, gy)) {
+        if (gb && !call.bias_rode) bias_grad_slabs(gy, gb, part + P.bias_off, N, K, OH * OW, st);
+        what = "conv2d_bwd_weight (split-16)";
+        break;
+    case WgradPlan::WGRAD2:
         nemar_wgrad2_launch(x0, C0, x1, C1, gy, gw, gb, N, H, W, K, OH, OW, R, S, stride, pad, pad_mode, g_wgrad_blocks,
                             g_wgrad != 2, g_dbg, part, st);
-        g_last_route = 0;
-        NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (wide)");
-        return NEMAR_OK;
+        what = "conv2d_bwd_weight (wide)";
+        break;
+    case WgradPlan::WGRAD2_PADDED_GY: {
+        float* gyp = part + P.gyp_off;
+        const long long total = (long long)N * K * P.ohv * OW;
+        hipLaunchKernelGGL(pad_planes_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, gy, gyp, OH * OW, P.ohv * OW, total);
+        nemar_wgrad2_launch(x0, C0, x1, C1, gyp, gw, gb, N, H, W, K, P.ohv, OW, R, S, stride, pad, pad_mode, g_wgrad_blocks,
+                            g_wgrad != 2, g_dbg, part, st);
+        what = "conv2d_bwd_weight (wide, padded gy)";
+        break;
     }
-    if (part && wgrad_pad_route(K, OH, OW, pad_mode)) {
-        const int ohv = padded_rows(OH, OW);
-        int splits, pps;
-        nemar_wgrad2_plan(K, J, N * ohv * OW, g_wgrad_blocks, &splits, &pps);
-        float* gyp = part + (((size_t)splits * ((size_t)K * J + K) + 3) & ~(size_t)3);       // 16-byte aligned, behind the slabs
-        const long long total = (long long)N * K * ohv * OW;
-        hipLaunchKernelGGL(pad_planes_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, gy, gyp, OH * OW, ohv * OW, total);
-        if (nemar_wgrad2_eligible(K, ohv, OW, gyp)) {
-            nemar_wgrad2_launch(x0, C0, x1, C1, gyp, gw, gb, N, H, W, K, ohv, OW, R, S, stride, pad, pad_mode, g_wgrad_blocks,
-                                g_wgrad != 2, g_dbg, part, st);
-            g_last_route = 0;
-            NEMAR_CHECK_LAUNCH("conv2d_bwd_weight (wide, padded gy)");
-            return NEMAR_OK;
-        }
+    case WgradPlan::LEGACY: {
+        WgradParams p;
+        p.src0 = x0; p.src1 = x1; p.C0 = C0; p.C1 = C1; p.Hs = H; p.Ws = W;
+        p.gy = gy; p.K = K; p.OH = OH; p.OW = OW;
+        p.gw = gw; p.gb = gb; p.J = J;
+        p.N = N; p.P = N * OH * OW; p.sy = stride; p.sx = stride; p.R = R; p.S = S; p.pad = pad; p.border = pad_mode;
+        p.fd_ohw = make_fastdiv(OH * OW); p.fd_ow = make_fastdiv(OW);
+        p.dbg = g_dbg;
+        p.pix_per_split = P.pix_per_split;
+        p.part = part;
+        p.partb = part ? part + P.bias_off : nullptr;
+        const bool wide = K > 32;
+        dim3 grid(nemar_cdiv(K, wide ? 128 : 32), nemar_cdiv(J, wide ? 128 : 256), P.splits), block(256);
+        if (wide) hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 2>), grid, block, 0, st, p);
+        if (part) nemar_sum_partials_pair(part, (long long)K * J, P.splits, gw, (long long)K * J, gb ? p.partb : nullptr, K, P.splits, gb, K, true, st);
     }
-    WgradParams p;
-    p.src0 = x0; p.src1 = x1; p.C0 = C0; p.C1 = C1; p.Hs = H; p.Ws = W;
-    p.gy = gy; p.K = K; p.OH = OH; p.OW = OW;
-    p.gw = gw; p.gb = gb; p.J = J;
-    p.N = N; p.P = N * OH * OW; p.sy = stride; p.sx = stride; p.R = R; p.S = S; p.pad = pad; p.border = pad_mode;
-    p.fd_ohw = make_fastdiv(OH * OW); p.fd_ow = make_fastdiv(OW);
-    p.dbg = g_dbg;
-    const bool wide = K > 32;
-    const int BM = wide ? 128 : 32, BN = wide ? 128 : 256;
-    const int mt = nemar_cdiv(K, BM), jt = nemar_cdiv(p.J, BN);
-    int splits;
-    legacy_wgrad_plan(K, p.J, p.P, &splits, &p.pix_per_split);
-    p.part = part;
-    p.partb = part ? part + (size_t)splits * K * J : nullptr;
-    dim3 grid(mt, jt, splits), block(256);
-    if (wide)
-        hipLaunchKernelGGL((wgrad_kernel<2, 2, 2, 2>), grid, block, 0, st, p);
-    else
-        hipLaunchKernelGGL((wgrad_kernel<1, 4, 1, 2>), grid, block, 0, st, p);
-    if (part) nemar_sum_partials_pair(part, (long long)K * J, splits, gw, (long long)K * J, gb ? p.partb : nullptr, K, splits, gb, K, true, st);
-    g_last_route = 0;
-    NEMAR_CHECK_LAUNCH("conv2d_bwd_weight");
+    }
+    NEMAR_CHECK_LAUNCH(what);
     return NEMAR_OK;
 }
 
@@ -1472,61 +997,46 @@ NEMAR_API int nemar_tune(int key, int value) {
 }
 #endif  // NEMAR_AB
 
+// the data-gradient plan of a layer's usual call (ConvFacts::canonical), for the queries below
+static DgradPlan usual_dgrad(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
+    DgradPlan P{};
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || R <= 0 || S <= 0 || stride < 1) return P;      // (nothing to plan)
+    return plan_dgrad({N, C, 0, H, W, K, R, S, stride, pad, pad_mode}, ConvFacts::canonical());
+}
+static bool fusable(const DgradPlan& P) { return P.gy_planes_need != 0 && P.split16_ksplit == 1; }
+
 // Scratch bytes nemar_conv2d_fwd / nemar_conv2d_bwd_data want for this layer (0: the layer never uses the arena)
 NEMAR_API size_t nemar_conv2d_scratch(int N, int H, int W, int K, int C, int R, int S, int stride, int pad) {
     if (N <= 0 || H <= 0 || W <= 0 || K <= 0 || C <= 0) return 0;
-    if (!g_split16 || !split16_worth_it(N, H + 2 * pad - R + 1, W + 2 * pad - S + 1, K, C, R, S)) return 0;
-    size_t b = 0;
-    if (nemar_split16_eligible(N, H, W, K, C, R, S, stride, pad, SPLIT16_ZERO, 4)) b = nemar_split16_scratch_total(N, H, W, K, C, H, W);
-    if (nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, SPLIT16_ZERO, 4)) {
-        const size_t d = nemar_split16_scratch_total(N, H, W, C, K, H, W);
-        if (d > b) b = d;
-    }
-    if (nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad)) {
-        const size_t d = nemar_split16_wgrad_scratch_bytes(N, C, H, W, K, R);
-        if (d > b) b = d;
-    }
-    return b;
+    return plan_arena_bytes({N, C, 0, H, W, K, R, S, stride, pad, BORDER_ZERO});
 }
 
-// bytes of the gy planes the data-gradient call of a layer can leave behind for its weight-gradient call (nemar_conv_extras.gy_planes_out /
-// .src2_planes); 0 = the layer's gradients do not both run on the wide route
+// bytes of the gy planes the data-gradient call can leave behind for the weight-gradient call (0: they do not both run on the wide route)
 NEMAR_API size_t nemar_conv2d_gy_planes_bytes(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
-    if (!g_dual_gy || !g_split16 || g_split16_variant != 4 || R != 3 || S != 3 || stride != 1 || pad != 1) return 0;
-    const int mode = pad_mode == BORDER_REFLECT ? SPLIT16_DGRAD_REFLECT : SPLIT16_ZERO;
-    if (!split16_worth_it(N, H, W, K, C, R, S) || !nemar_split16_eligible(N, H, W, C, K, R, S, stride, pad, mode, g_split16_variant) ||
-        !nemar_split16_wgrad_eligible(N, C, H, W, K, R, S, stride, pad))
-        return 0;
-    return nemar_split16_wgrad_g_bytes(N, H, W, K, R);
+    return usual_dgrad(N, C, H, W, K, R, S, stride, pad, pad_mode).gy_planes_need;
 }
 
-// 1 when nemar_conv2d_bwd_data_ex of this layer honours nemar_conv_extras.addend / .out_max_words and takes gy as producer-written planes
-// (.src_planes), and its nemar_conv2d_bwd_weight_ex takes both operands as planes: the wide 3x3 route with an unsplit reduction
+// 1 when the data-gradient call honours addend / out_max_words and both gradient calls take planes: the wide 3x3 route, reduction unsplit
 NEMAR_API int nemar_conv2d_bwd_data_fusable(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
-    if (nemar_conv2d_gy_planes_bytes(N, C, H, W, K, R, S, stride, pad, pad_mode) == 0) return 0;
-    return nemar_split16_ksplit(N, H, W, C, K) == 1 ? 1 : 0;
+    return fusable(usual_dgrad(N, C, H, W, K, R, S, stride, pad, pad_mode)) ? 1 : 0;
 }
 
-// 1 when nemar_conv2d_bwd_data_ex of this layer (one destination, no bias, no activation) adds nemar_conv_extras.addend to the data gradient:
-// the wide route's fused epilogue, or a stride-1 reflect layer whose data gradient ends with a fold pass (the general 16-bit-pipe kernel
-// on the padded domain + fold; the tiny maps' split launch + sum-and-fold) — the addend is one more term of that pass.
+// 1 when the usual data-gradient call adds nemar_conv_extras.addend: the wide route's fused epilogue, or a stride-1 reflect layer whose data
+// gradient ends with a fold pass.  Not a layer any operator's wide route may take, nor a 7x7 layer (open items).
 NEMAR_API int nemar_conv2d_bwd_data_addend_ok(int N, int C, int H, int W, int K, int R, int S, int stride, int pad, int pad_mode) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) return 0;
-    if (nemar_conv2d_bwd_data_fusable(N, C, H, W, K, R, S, stride, pad, pad_mode)) return 1;
-    if (pad_mode != BORDER_REFLECT || pad <= 0 || stride != 1 || pad >= H || pad >= W || R != S) return 0;
-    if (nemar_conv2d_scratch(N, H, W, K, C, R, S, stride, pad) > 0) return 0;      // a layer the wide route takes when its arena is given
-    if (R == 7) return 0;                                                            // (the 7x7 kernels have their own borders)
-    const DgradLayout L = dgrad_layout(N, C, H, W, K, R, S, stride, pad, pad_mode);
-    return (L.fold16 || L.fold) ? 1 : 0;
+    const DgradPlan P = usual_dgrad(N, C, H, W, K, R, S, stride, pad, pad_mode);
+    if (fusable(P)) return 1;
+    if (pad_mode != BORDER_REFLECT || pad <= 0 || stride != 1 || pad >= H || pad >= W || R != S || R == 7) return 0;
+    return (P.fold16 || P.fold) && plan_arena_bytes({N, C, 0, H, W, K, R, S, stride, pad, BORDER_ZERO}) == 0 ? 1 : 0;
 }
 
 // 1 when the last nemar_conv2d_bwd_data_ex call on this thread filled its gy_planes_out buffer (the route it took supports it): only then
 // may the buffer be handed to nemar_conv2d_bwd_weight_ex as src2_planes
 NEMAR_API int nemar_last_gy_planes(void) { return g_last_gy_planes; }
 
-// ---- the C-ABI entry points of the three operators.  The side inputs of the wide-layer route (scratch arena, per-sample max words,
-// producer-written planes) travel WITH the call (nemar_conv_extras): nothing is registered, per process or per thread.  Each _ex entry
-// copies the members its operator documents into the ConvCall the operator runs with; the plain entries run with an empty one.
+// ---- the C-ABI entry points of the three operators.  The side inputs of the wide-layer route (scratch arena, per-sample max words, producer-
+// written planes) travel WITH the call (nemar_conv_extras): each _ex entry copies the members its operator documents into the ConvCall the
+// operator runs with; the plain entries run with an empty one.
 namespace {
 // what every operator takes: the arena and the source's max words
 ConvCall call_from(const nemar_conv_extras* ex) {
@@ -1653,20 +1163,11 @@ NEMAR_API int nemar_bias_grad(const float* g, float* gb, int N, int C, int HW, v
                               void* stream) {
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(g && gb && N > 0 && C > 0 && HW > 0, "bias_grad: bad arguments");
-    const int chunks = nemar_cdiv(HW, BIAS_CHUNK);
-    if (g_deterministic) {
-        const size_t need = nemar_bias_grad_workspace(N, C, HW);
-        if (!workspace || ws_bytes < need) {
-            nemar_set_error("bias_grad: workspace %zu < %zu", workspace ? ws_bytes : (size_t)0, need);
-            return NEMAR_EWORKSPACE;
-        }
-        hipLaunchKernelGGL(bias_grad_kernel, dim3(C, N, chunks), dim3(256), 0, (hipStream_t)stream, g, (float*)workspace, N, C,
-                           HW, BIAS_CHUNK);
-        nemar_sum_partials((const float*)workspace, C, N * chunks, gb, C, true, (hipStream_t)stream);
-    } else {
-        hipLaunchKernelGGL(bias_grad_atomic_kernel, dim3(C, N, chunks), dim3(256), 0, (hipStream_t)stream, g, gb, N, C, HW,
-                           BIAS_CHUNK);
+    if (g_deterministic && (!workspace || ws_bytes < nemar_bias_grad_workspace(N, C, HW))) {
+        nemar_set_error("bias_grad: workspace %zu < %zu", workspace ? ws_bytes : (size_t)0, nemar_bias_grad_workspace(N, C, HW));
+        return NEMAR_EWORKSPACE;
     }
+    bias_grad_slabs(g, gb, g_deterministic ? (float*)workspace : nullptr, N, C, HW, (hipStream_t)stream);
     NEMAR_CHECK_LAUNCH("bias_grad");
     return NEMAR_OK;
 }

@@ -731,7 +731,7 @@ S16gPlan nemar_s16g_plan(const S16gProblem& q) {
     const int C = q.C0 + q.C1;
     if (q.ncls < 1 || q.ncls > S16G_MAX_CLS || (q.sstride != 1 && q.sstride != 2) || q.M < 5 || C < 1) return pl;       // (<= 4 rows: the narrow VALU kernels)
     if (q.ncls > 1 && q.sstride != 1) return pl;
-    if (q.act == ACT_TANH) return pl;
+    if (q.act == ACT_TANH) return pl;      // (the ONLY use of q.act here: conv_route.h plan_dgrad re-uses one plan for every other epilogue)
     int maxtaps = 0, dymin = 1 << 20, dymax = -(1 << 20), dxmin = 1 << 20, dxmax = -(1 << 20), OH = 0, OW = 0;
     for (int c = 0; c < q.ncls; ++c) {
         if (q.ntaps[c] < 1 || q.ntaps[c] > (q.ncls > 1 ? S16G_CLS_TAPS : S16G_MAX_TAPS)) return pl;

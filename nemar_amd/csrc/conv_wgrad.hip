@@ -423,8 +423,8 @@ void launch_wgrad2(const Wgrad2Params& p, bool vec, dim3 grid, hipStream_t st) {
 
 // Shapes this kernel takes: layers whose gy rows can be read in aligned 16-byte chunks that never straddle two
 // images (OH*OW % 4 == 0).  Everything else stays on the VGPR-staged kernel in conv.hip.
-bool nemar_wgrad2_eligible(int K, int OH, int OW, const float* gy) {
-    return K > 4 && (OH * OW) % 4 == 0 && (reinterpret_cast<uintptr_t>(gy) & 15) == 0;
+bool nemar_wgrad2_eligible(int K, int OH, int OW, bool gy_aligned16) {
+    return K > 4 && (OH * OW) % 4 == 0 && gy_aligned16;
 }
 
 // Split plan shared by the workspace query and the launch.  The pixel reduction is split so that the grid is ONE full
