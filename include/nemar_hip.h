@@ -57,7 +57,21 @@ int nemar_grid_sample_fwd(const float* in, const float* grid_src, int grid_mode,
  * own position, 64-bit fixed-point atomics (40 bits below max |gout|) for the others; the affine grid gradient is summed
  * in a fixed order.  Workspace contract: nemar_grid_sample_bwd_workspace() bytes, of which the leading
  * nemar_grid_sample_bwd_zeroed_bytes() must be ZERO on entry of the first call and are left zero by every call (the
- * fixed-point accumulator); the rest is scratch.  workspace == NULL: fp32-atomic scatter (any shape; not reproducible). */
+ * fixed-point accumulator); the rest is scratch.  workspace == NULL: fp32-atomic scatter (any shape; not reproducible).
+ * Range of the fixed-point path.  A contribution w * gout is rounded to a multiple of 2^(e - 40), 2^(e-1) <= m < 2^e, m the largest
+ * |gout| of the tiles that have such pixels (at most the call's): an error of at most 2^-40 * max |gout| each.  That holds for
+ * 2^-81 <= m and up to the largest finite float; e is clamped at -80, so below that (m = 0 included) the step is 2^-120 whatever m
+ * is.  Scaling gout by a power of two scales gin and ggrid by it bit for bit while m stays in that range and nothing leaves the
+ * normal floats.  Headroom: the accumulator holds (contributions to one texel) * 2^40 and must stay below 2^63, i.e. fewer than 2^23
+ * output pixels may land on one texel.
+ * Non-finite data.  Whatever gout and grid_src hold, the call returns NEMAR_OK, the zeroed bytes come back zero and the next call on
+ * the workspace is what it would be on a fresh one.  A NaN or Inf in gout reaches d loss / d grid of its own pixel (NaN or +-Inf) and
+ * the at most four texels of its channel that the pixel samples: NaN or +-Inf from the gather, and from the fixed-point path NaN, +-Inf
+ * or a finite value without meaning (the conversion of a NaN or Inf to the accumulator's integer is not specified).  Everything else
+ * keeps the bound above — with one exception: an INFINITE gout in a tile that has fixed-point pixels becomes m, and every finite
+ * fixed-point contribution of that call then rounds to zero (finite, but the far part of grad_input is lost).  A NaN never becomes m.
+ * A non-finite grid_src value sends its pixel outside the plane: no contribution to grad_input, NaN or 0 in its own ggrid elements
+ * (nemar_grid_sample_fwd writes NaN for that pixel where torch writes 0). */
 size_t nemar_grid_sample_bwd_workspace(int N, int C, int H, int W);
 size_t nemar_grid_sample_bwd_zeroed_bytes(int N, int C, int H, int W);
 int nemar_grid_sample_bwd(const float* in, const float* grid_src, int grid_mode, const float* gout,

@@ -21,6 +21,16 @@ def _assert_close(got, want, atol, rtol=0.0, what=""):
 
 
 # ------------------------------------------------------------------------------------------------
+def affine_grid_f32(src, Ho, Wo):
+    """the sampling grid [N,Ho,Wo,2] of GRID_AFFINE parameters src [N,6] in float32 with the kernel's exact operation order"""
+    f32 = np.float32
+    th = src + np.array([1, 0, 0, 0, 1, 0], dtype=f32)[None]
+    xb = ((f32(2) * np.arange(Wo, dtype=f32) + f32(1)) / f32(Wo) - f32(1))[None, None, :]
+    yb = ((f32(2) * np.arange(Ho, dtype=f32) + f32(1)) / f32(Ho) - f32(1))[None, :, None]
+    T = lambda i: th[:, i][:, None, None]
+    return np.stack([(T(0) * xb + T(1) * yb) + T(2), (T(3) * xb + T(4) * yb) + T(5)], axis=-1).astype(f32)
+
+
 def case_grid_sample(be, mode, N, C, H, W, Ho, Wo, scale, seed=0, need_gin=True, accumulate=False, workspace=True,
                      atomic=False, smooth_px=None):
     """smooth_px = (shift_x, shift_y, wave) in pixels (GRID_UNET / GRID_EXPLICIT): a smooth LARGE deformation — a translation plus a
@@ -45,11 +55,7 @@ def case_grid_sample(be, mode, N, C, H, W, Ho, Wo, scale, seed=0, need_gin=True,
         grid = O.unet_grid(src)                                   # float32, fma-exact linspace + offsets
     elif mode == GRID_AFFINE:
         src = (rng.standard_normal((N, 6)) * scale).astype(f32)
-        th = src + np.array([1, 0, 0, 0, 1, 0], dtype=f32)[None]
-        xb = ((f32(2) * np.arange(Wo, dtype=f32) + f32(1)) / f32(Wo) - f32(1))[None, None, :]
-        yb = ((f32(2) * np.arange(Ho, dtype=f32) + f32(1)) / f32(Ho) - f32(1))[None, :, None]
-        T = lambda i: th[:, i][:, None, None]
-        grid = np.stack([(T(0) * xb + T(1) * yb) + T(2), (T(3) * xb + T(4) * yb) + T(5)], axis=-1).astype(f32)
+        grid = affine_grid_f32(src, Ho, Wo)
     else:
         src = O.unet_grid(offsets())
         grid = src
