@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 606 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 607 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -492,6 +492,33 @@ int nemar_label_overlap(const float* labels_moving, const float* labels_fixed, c
  * A NaN coordinate (a missing annotation) gives a NaN pair.  One lane per point, plain fp32. */
 int nemar_map_points(const float* pts, const float* pred, int grid_mode, float* out, int N, int P, int Hs, int Ws, int hf, int wf,
                      int Ho, int Wo, void* stream);
+
+/* Composing two predictions (csrc/compose.hip; not in the reference, which applies one): ONE prediction that samples where two would in
+ * sequence, so that a second look at an already-registered pair (a "recursive cascade"), or a registration carried over from an earlier
+ * run, interpolates the image once — and so that nemar_warp_resampled_fwd, nemar_label_overlap and nemar_map_points, which read one
+ * transformation, can apply and score the pair.
+ * `first` (P1: first_mode, field size h1 x w1) is applied to the image first, A1(x) = A(S1(x)); `second` (P2: second_mode, h2 x w2) to
+ * the result, A2(x) = A1(S2(x)) = A(S1(S2(x))).  Operands as nemar_warp_resampled_fwd takes them: NEMAR_GRID_UNET offsets [N,2,h,w] or
+ * NEMAR_GRID_AFFINE dtheta [N,6] (h, w ignored); NEMAR_GRID_EXPLICIT is NEMAR_EINVAL.  At the composition size (H,W), for output pixel (h,w):
+ *   (gx2, gy2) = the normalised coordinate nemar_warp_resampled_fwd computes for P2 at output size (H,W) (a UNet field resized in registers
+ *                whenever (h2,w2) != (H,W));
+ *   p          = ((gx2 + 1) * W - 1) / 2, ((gy2 + 1) * H - 1) / 2: the pixel position in the intermediate image, which has the same size;
+ *   (gx1, gy1) = the continuous extension of P1's grid at p for output size (H,W), exactly what nemar_map_points evaluates before it
+ *                unnormalises (beyond the border: the border texel of a UNet field, the linearly extended identity);
+ *   out_field[n,0,h,w] = gx1 - linspace(-1,1,W)[w],  out_field[n,1,h,w] = gy1 - linspace(-1,1,H)[h].
+ * The composite is always a NEMAR_GRID_UNET offset field [N,2,H,W], whatever the two modes were.  A zero UNet prediction is the
+ * reference's slight zoom (linspace under align_corners=False), not the identity, and composition keeps that faithfully: compose(P1, 0) != P1.
+ * (The identity is NEMAR_GRID_AFFINE with dtheta = 0.)
+ * Optional fused warp, img [N,C,H,W] and out_img [N,C,H,W] both given or both NULL: out_img is bit for bit what
+ * nemar_warp_resampled_fwd(img, out_field, NEMAR_GRID_UNET, NEMAR_SAMPLE_BILINEAR, out_img, N, C, H, W, H, W, H, W) writes — the moving
+ * image of the next cascade pass, produced while the position is in registers; out_field is the same bits with and without it.
+ * Plain fp32, no atomics, no workspace: bitwise repeatable.
+ * NEMAR_EINVAL, nothing launched: NEMAR_GRID_EXPLICIT (or no mode at all) on either side; first, second or out_field NULL; exactly one
+ * of img / out_img; any given pointer not 4-byte aligned (that is all the alignment asked for); C < 1 with img; a non-positive N, H or W;
+ * h or w < 1 on a NEMAR_GRID_UNET side; N > 65535; H*W >= 2^31 (a field plane >= 2^30); out_field equal to first or second, or out_img
+ * equal to an operand, img or out_field (the kernel gathers from them). */
+int nemar_compose_pred(const float* first, int first_mode, int h1, int w1, const float* second, int second_mode, int h2, int w2,
+                       float* out_field, const float* img, float* out_img, int C, int N, int H, int W, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

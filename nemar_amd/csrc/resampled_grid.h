@@ -1,5 +1,6 @@
-// Where nemar_warp_resampled_fwd samples, for every kernel that must sample THERE: register.hip (the warp itself) and score.hip
-// (nemar_label_overlap, which counts the labels that warp would write without writing them).  The 64 x 16 output tile, the coarse-field
+// Where nemar_warp_resampled_fwd samples, for every kernel that must sample THERE: register.hip (the warp itself), score.hip
+// (nemar_label_overlap, which counts the labels that warp would write without writing them) and compose.hip (nemar_compose_pred, which
+// reads one prediction where another samples).  The 64 x 16 output tile, the coarse-field
 // patch a tile stages in LDS, the pixel's grid coordinate from it, and the texel(s) that coordinate reads — one statement of the
 // arithmetic on top of warp_grid.h and resize_taps.h, so that the two cannot drift apart.
 #pragma once
@@ -22,6 +23,26 @@ __device__ __forceinline__ RegSrc field_at(const float* f, int pitch, int cstep,
     const float* g = f + cstep;
     return RegSrc{resize_blend(f[r0 + c0], f[r0 + c1], f[r1 + c0], f[r1 + c1], tw, th),
                   resize_blend(g[r0 + c0], g[r0 + c1], g[r1 + c0], g[r1 + c1], tw, th)};
+}
+
+// the CONTINUOUS extension of a prediction's grid at output size (Ho, Wo): the normalised coordinate at the position (px, py), in pixels,
+// between or beyond the pixels — at an integer position inside the image, the pixel's own coordinate.  UNET: the align_corners=False resize
+// of the sample's field fN [2,hf,wf] evaluated at the position (tap1d_at: the border texel outside the image) added to the linearly
+// extended identity; AFFINE: theta applied to the base coordinate.  One statement for score.hip (nemar_map_points: annotated points) and
+// compose.hip (nemar_compose_pred: where the second prediction's sampling position reads the first)
+template <int MODE>
+__device__ __forceinline__ void grid_at(const float* __restrict__ fN, int hf, int wf, float sh, float sw, const float* th, float px, float py,
+                                        int Ho, int Wo, float& gx, float& gy) {
+    if (MODE == GRID_UNET) {
+        const Tap1D ty = tap1d_at(py, hf, sh), tx = tap1d_at(px, wf, sw);
+        const RegSrc d = field_at(fN, wf, hf * wf, 0, 0, ty, tx);
+        gx = linspace_at(px, Wo) + d.x();
+        gy = linspace_at(py, Ho) + d.y();
+    } else {
+        const float xb = affine_base_at(px, Wo), yb = affine_base_at(py, Ho);
+        gx = th[0] * xb + th[1] * yb + th[2];
+        gy = th[3] * xb + th[4] * yb + th[5];
+    }
 }
 
 // where one output pixel reads the source: up to four texel offsets (clamped into the image, so that the loads are unconditional and the

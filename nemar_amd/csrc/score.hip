@@ -125,17 +125,12 @@ __global__ __launch_bounds__(64) void map_points_kernel(const float* __restrict_
     const float px = missing ? 0.f : qx, py = missing ? 0.f : qy;
     float gx, gy;
     if (mode == GRID_UNET) {
-        // the offsets at the point: the align_corners=False resize of `pred` evaluated at a continuous coordinate (resize_taps.h)
-        const Tap1D ty = tap1d_at(py, hf, sh), tx = tap1d_at(px, wf, sw);
-        const RegSrc d = field_at(pred + (size_t)n * 2 * hf * wf, wf, hf * wf, 0, 0, ty, tx);
-        gx = linspace_at(px, Wo) + d.x();
-        gy = linspace_at(py, Ho) + d.y();
+        // the offsets at the point: the align_corners=False resize of `pred` evaluated at a continuous coordinate (resampled_grid.h)
+        grid_at<GRID_UNET>(pred + (size_t)n * 2 * hf * wf, hf, wf, sh, sw, nullptr, px, py, Ho, Wo, gx, gy);
     } else {
         float th[6];
         affine_theta(pred, n, th);
-        const float xb = affine_base_at(px, Wo), yb = affine_base_at(py, Ho);
-        gx = th[0] * xb + th[1] * yb + th[2];
-        gy = th[3] * xb + th[4] * yb + th[5];
+        grid_at<GRID_AFFINE>(nullptr, hf, wf, sh, sw, th, px, py, Ho, Wo, gx, gy);
     }
     float ix, iy;
     sample_position(gx, gy, Ws, Hs, ix, iy);

@@ -202,6 +202,36 @@ class NEMARModel(BaseModel):
         cols[2] = rows[:, 2].max()
         return registration_summary(cols.tolist(), self.gt_field.size(0) * self.gt_field.size(2) * self.gt_field.size(3))
 
+    def cascade(self, passes):
+        """test() with `passes` looks at the set_input pair (a "recursive cascade"): pass 1 is test() exactly as it is; every further pass
+        predicts from (registered_real_A, real_B), composes that prediction ONTO the accumulated one (netR.compose: one transformation
+        that samples where the two would in sequence) and warps the ORIGINAL real_A by the composite — one interpolation however many
+        passes, the UNet STN's in the composing launch itself.  Afterwards netR.last_prediction() is the composite, registered_real_A and
+        fake_RT_B are warps by it and fake_TR_B = netT(registered_real_A), so register() and registration_error() work unchanged.
+        cascade(1) is test().  Inference only: no autograd, no regularisation term for the further passes."""
+        passes = int(passes)
+        if passes < 1:
+            raise ValueError('cascade: %d passes (at least 1)' % passes)
+        self.test()
+        if passes == 1:
+            return
+        with torch.no_grad():
+            acc = self.netR.last_prediction()
+            dense = acc[1] == ops.GRID_UNET
+            for _ in range(passes - 1):
+                self.netR.predict(self.registered_real_A, self.real_B)
+                new = self.netR.last_prediction()
+                if dense:
+                    field, self.registered_real_A = self.netR.compose(acc, new, self.real_A)
+                else:
+                    field = self.netR.compose(acc, new)
+                    self.registered_real_A = self.netR.apply(field, [self.real_A])[0]
+                acc = (field, acc[1])
+            self.netR.set_last_prediction(acc[0])
+            self.fake_RT_B = self.netR.apply(acc, [self.fake_B])[0]
+            self.fake_TR_B = self.netT(self.registered_real_A)
+            self.compute_visuals()
+
     def register(self, full_A, full_B=None, labels_A=None, translate=True, labels_B=None, landmarks_A=None, landmarks_B=None,
                  num_classes=None):
         """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the

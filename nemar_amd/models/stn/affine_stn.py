@@ -100,6 +100,22 @@ class AffineSTN(nn.Module):
         (ops.map_points).  No autograd."""
         return ops.map_points(prediction_tensor(field), ops.GRID_AFFINE, pts, src_hw, out_hw)
 
+    def compose(self, first, second):
+        """ONE dtheta [N,6] that samples where `first` and then `second` would in sequence — an affine cascade stays affine, in closed
+        form and exactly: under align_corners=False the base coordinate of the position S2(x) samples is theta2 applied to the base
+        coordinate of x, so theta12 = theta1 o theta2 as 3 x 3 matrices (formed in float64, rounded once).  No kernel, no autograd."""
+        import torch
+        d1, d2 = prediction_tensor(first).detach(), prediction_tensor(second).detach()
+        eye = torch.eye(3, dtype=torch.float64, device=d1.device)
+
+        def matrix(d):          # dtheta [N,6] -> [N,3,3]: theta = dtheta + I over the row (0, 0, 1)
+            return torch.cat([d.to(torch.float64).view(-1, 2, 3), torch.zeros_like(eye[None, 2:]).expand(d.size(0), 1, 3)], 1) + eye
+        return ((matrix(d1) @ matrix(d2)) - eye)[:, :2].reshape(-1, 6).to(torch.float32)
+
+    def set_last_prediction(self, dtheta):
+        """what last_prediction() returns from now on: a composite made outside the forward pass (NEMARModel.cascade)"""
+        self.last_dtheta = dtheta.detach()
+
     def fork_field(self, field, n_warps):
         """-> ([one theta handle per warp() call], the handle for regularization()) — ops.fork, as UnetSTN.fork_field"""
         hs = ops.fork(field, n_warps + 1)

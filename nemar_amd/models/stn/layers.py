@@ -147,3 +147,12 @@ def prediction_tensor(field):
     if not tensors:
         raise TypeError('not an STN prediction: %r' % (field,))
     return tensors[-1]
+
+
+def prediction_mode(field, default):
+    """The grid mode of a prediction in any of prediction_tensor's forms: what a `(tensor, grid mode)` pair says, else `default` (the
+    mode of the STN that was asked)."""
+    import torch
+    if not torch.is_tensor(field) and len(field) == 2 and torch.is_tensor(field[0]) and isinstance(field[1], int):
+        return field[1]
+    return default

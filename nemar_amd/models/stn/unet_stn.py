@@ -15,7 +15,7 @@ typo); the low-res upsample branch fires only if BOTH dims differ (B3).
 import torch.nn as nn
 
 from ... import ops
-from .layers import Conv, DownBlock, ResnetTransformer, prediction_tensor
+from .layers import Conv, DownBlock, ResnetTransformer, prediction_mode, prediction_tensor
 from .stn_losses import smoothness_loss
 
 sampling_align_corners = False
@@ -154,6 +154,20 @@ class UnetSTN(nn.Module):
         """Where the prediction samples the src_hw source for points [N,P,2] (x, y) given in pixels of the out_hw fixed image
         (ops.map_points).  No autograd."""
         return ops.map_points(prediction_tensor(field), ops.GRID_UNET, pts, src_hw, out_hw)
+
+    def compose(self, first, second, image=None):
+        """ONE prediction that samples where `first` and then `second` would in sequence — `second` was predicted from the pair `first`
+        had already registered (a cascade pass), or `first` comes from an earlier run: the composite offsets [N,2,oh,ow] at the network's
+        size (ops.compose_predictions), which apply(), overlap() and map_points() take like any prediction of this network.  Either
+        operand may be a `(tensor, grid mode)` pair of another STN (an affine pre-registration).  With image [N,C,oh,ow] returns
+        (offsets, image warped by them), from the same launch.  A zero field is the reference's slight zoom, not the identity, and
+        composing keeps it: compose(first, zeros) != first.  No autograd."""
+        return ops.compose_predictions(prediction_tensor(first), prediction_mode(first, ops.GRID_UNET), prediction_tensor(second),
+                                       prediction_mode(second, ops.GRID_UNET), (self.oh, self.ow), image)
+
+    def set_last_prediction(self, offsets):
+        """what last_prediction() returns from now on: a composite made outside the forward pass (NEMARModel.cascade)"""
+        self.last_offsets = offsets.detach()
 
     def fork_field(self, field, n_warps):
         """-> ([one field per warp() call], the field for regularization()): handles of the same tensors (ops.fork), so that the

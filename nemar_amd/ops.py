@@ -1768,6 +1768,30 @@ def map_points(pred, grid_mode, pts, src_hw, out_hw):
     return out
 
 
+def compose_predictions(first, first_mode, second, second_mode, out_hw, image=None):
+    """ONE prediction that samples where two would in sequence (nemar_compose_pred): `first` is applied to the image first, `second` to
+    the result — A2(x) = A(S1(S2(x))).  Each is offsets [N,2,h,w] (GRID_UNET; its own size, resized inside the kernel) or dtheta [N,6]
+    (GRID_AFFINE).  Returns the composite, always a GRID_UNET offset field [N,2,H,W] at out_hw = (H, W), which warp_resampled,
+    label_overlap and map_points read like any UNet prediction.  With image [N,C,H,W] returns (field, warped): the image warped
+    bilinearly by the composite in the same launch, bit for bit warp_resampled(field, GRID_UNET, [image], None)[0].  A zero UNet
+    prediction is the reference's slight zoom, not the identity (that is GRID_AFFINE zeros [N,6]).  No autograd, no sync."""
+    first, N, h1, w1 = _prediction("compose_predictions", first, first_mode)
+    second, N2, h2, w2 = _prediction("compose_predictions", second, second_mode)
+    if N2 != N:
+        raise ValueError("compose_predictions: predictions of %d and %d samples" % (N, N2))
+    H, W = int(out_hw[0]), int(out_hw[1])
+    field = torch.empty((N, 2, H, W), dtype=torch.float32, device=first.device)
+    warped, C = None, 0
+    if image is not None:
+        image = _c(image.detach())
+        if image.dim() != 4 or image.shape[0] != N or tuple(image.shape[2:]) != (H, W):
+            raise ValueError("compose_predictions: image %s, expected [%d,C,%d,%d]" % (tuple(image.shape), N, H, W))
+        C = int(image.shape[1])
+        warped = torch.empty_like(image)
+    L.compose_pred(_p(first), first_mode, h1, w1, _p(second), second_mode, h2, w2, _p(field), _p(image), _p(warped), C, N, H, W, _stream())
+    return field if image is None else (field, warped)
+
+
 # ---- known misalignment: ground-truth fields, the deforming input pipeline, the registration-error meter (no autograd: data and read-outs) ----
 def deform_field(params, B, Hc, Wc, gh, gw):
     """params [B, 6 + 2*gh*gw] (a11 a12 tx a21 a22 ty about the crop centre, then a [2,gh,gw] lattice of pixel displacements; gh = gw = 0:

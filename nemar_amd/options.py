@@ -132,5 +132,7 @@ class TestOptions(BaseOptions):
         a('--phase', type=str, default='test')
         a('--eval', action='store_true')
         a('--num_test', type=int, default=50)
+        # (MI355X build) python -m nemar_amd.register: looks at every pair, each from the pair the previous ones registered (NEMARModel.cascade)
+        a('--passes', type=int, default=1)
         self.isTrain = False
         return parser

@@ -10,11 +10,14 @@ result against is optional too: `labels_B.npy` ([M,H,W] or [M,1,H,W], the size o
 network's --img_height x --img_width by the dataset's own resize and normalise path, netR predicts the transformation ONCE at that size
 (weights of --epoch under --checkpoints_dir/--name, the flags the model was trained with), and NEMARModel.register() applies it to the
 full-size images: the sampling grid is in normalised coordinates, so the prediction holds at every size (csrc/register.hip).
+With --passes K (default 1) netR looks K times, each time at the pair its earlier predictions registered, and the K predictions are
+composed into ONE transformation (NEMARModel.cascade, csrc/compose.hip): every image and label map is still interpolated once.
 
 Written under --results_dir/--name/:
     registered_A.npy          modality A registered to B, in A.npy's own size, layout and dtype (uint8: rounded and clamped on the host)
     registered_labels_A.npy   labels_A.npy warped with nearest sampling (class ids are copied, never blended), in its own dtype
-    offsets.npy               the network-resolution predictions: offsets [M,2,h,w] (unet) or dtheta [M,6] (affine)
+    offsets.npy               the network-resolution predictions: offsets [M,2,h,w] (unet) or dtheta [M,6] (affine); with --passes K > 1 the
+                              composite of the K predictions, in the same form
     scores.json               only with labels_A.npy + labels_B.npy and / or the two landmark files (score_summary below): per-class and mean
                               Dice before and after registration, from the counts of the whole data set; mean, median and max
                               distance in pixels between the mapped landmarks of B and those of A, before and after, and how many
@@ -133,7 +136,7 @@ def main(argv=None):
     for i0 in range(0, M, opt.batch_size):
         idx = list(range(i0, min(M, i0 + opt.batch_size)))
         model.set_input(network_batch(pool_A, pool_B, idx, opt))
-        model.test()
+        model.cascade(opt.passes)
         part = lambda t: None if t is None else t[idx[0]:idx[-1] + 1]
         out = model.register(part(pool_A), part(pool_B), part(labels), translate=False,          # (fake_RT_B is not among the files this command writes)
                              labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes)
@@ -161,8 +164,8 @@ def main(argv=None):
         if scores.get('tre_px', {}).get('points'):
             told += ', mean TRE %.3f -> %.3f px over %d points' % (scores['tre_px']['before']['mean'], scores['tre_px']['after']['mean'], scores['tre_px']['points'])
     torch.cuda.synchronize()
-    print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s, %.2f s -> %s'
-          % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width,
+    print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s%s, %.2f s -> %s'
+          % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width, '' if opt.passes == 1 else ' in %d passes' % opt.passes,
              '' if labels is None else ', labels %dx%d' % tuple(labels.shape[2:]), told, time.time() - t0, out_dir))
 
 
