@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 607 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 608 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -519,6 +519,33 @@ int nemar_map_points(const float* pts, const float* pred, int grid_mode, float* 
  * equal to an operand, img or out_field (the kernel gathers from them). */
 int nemar_compose_pred(const float* first, int first_mode, int h1, int w1, const float* second, int second_mode, int h2, int w2,
                        float* out_field, const float* img, float* out_img, int C, int N, int H, int W, void* stream);
+
+/* Regularity of a registration (csrc/regularity.hip; not in the reference, which has no evaluation code): the Jacobian determinant of
+ * the transformation a prediction describes, as a map and as fold / log-Jacobian statistics, at the size the images are registered at,
+ * in one pass over the output.  pred, grid_mode, hf and wf are what nemar_warp_resampled_fwd takes (NEMAR_GRID_UNET offsets
+ * [N,2,hf,wf], resized in registers; NEMAR_GRID_AFFINE dtheta [N,6], hf and wf ignored; NEMAR_GRID_EXPLICIT is NEMAR_EINVAL).
+ * For output pixel (h,w) of size (Ho,Wo):
+ *   (gx, gy) = the normalised coordinate nemar_warp_resampled_fwd, nemar_label_overlap and nemar_compose_pred compute for it (the same bits);
+ *   p(h,w)   = ((gx + 1) * Wo - 1) / 2, ((gy + 1) * Ho - 1) / 2: the position in pixels of an image of the OUTPUT's own size (the p of
+ *              nemar_compose_pred), so that the determinant does not depend on the source image's size and a pure resize has determinant 1;
+ *   interior = h < Ho-1 and w < Wo-1: the pixel has both forward neighbours (nemar_registration_error's rule);
+ *   det      = a.x * b.y - b.x * a.y with a = p(h,w+1) - p(h,w), b = p(h+1,w) - p(h,w), at interior pixels (nemar_registration_error's
+ *              forward-difference expression); a FOLD is det <= 0.
+ * det_out [N,Ho,Wo] or NULL: det at interior pixels, a quiet NaN in the last row and the last column; 4-byte alignment is all it needs.
+ * counts [N,2] uint32 = (interior, folds), exact.  stats [N,5] = (min det, max det, sum det, sum log det, sum (log det)^2): min, max
+ * and sum det over the interior pixels; the two log sums over the interior pixels with det > 0, of which there are interior - folds
+ * (SDlogJ = sqrt(sum2 / k - (sum1 / k)^2) is the caller's arithmetic, in double).  Without an interior pixel (Ho == 1 or Wo == 1):
+ * counts = (0, 0), min = +inf, max = -inf, sums 0.  Every statistic is a function of exactly the det values the map holds, and counts and
+ * stats are the same bits with and without det_out.  A zero UNet prediction is the reference's slight zoom (linspace under
+ * align_corners=False): det = Wo Ho / ((Wo-1)(Ho-1)); NEMAR_GRID_AFFINE gives theta's 2 x 2 determinant at every pixel.
+ * Per-workgroup partials (one per 64 x 16 output tile) go to the workspace and are merged in a fixed order: no atomics, bitwise
+ * repeatable.
+ * NEMAR_EINVAL, nothing launched: pred, counts, stats or workspace NULL; any given pointer not 4-byte aligned; a grid_mode other than
+ * NEMAR_GRID_UNET / NEMAR_GRID_AFFINE; a non-positive N, Ho or Wo; hf or wf < 1 with NEMAR_GRID_UNET; N > 65535; Ho*Wo >= 2^31 (a field
+ * plane >= 2^30, Ho > 16 * 65535); det_out equal to pred; ws_bytes < nemar_jacobian_stats_workspace(). */
+size_t nemar_jacobian_stats_workspace(int N, int Ho, int Wo);
+int nemar_jacobian_stats(const float* pred, int grid_mode, float* det_out, unsigned* counts, float* stats, void* workspace,
+                         size_t ws_bytes, int N, int hf, int wf, int Ho, int Wo, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

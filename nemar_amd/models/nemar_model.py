@@ -202,19 +202,22 @@ class NEMARModel(BaseModel):
         cols[2] = rows[:, 2].max()
         return registration_summary(cols.tolist(), self.gt_field.size(0) * self.gt_field.size(2) * self.gt_field.size(3))
 
-    def cascade(self, passes):
+    def cascade(self, passes, regularity=False):
         """test() with `passes` looks at the set_input pair (a "recursive cascade"): pass 1 is test() exactly as it is; every further pass
         predicts from (registered_real_A, real_B), composes that prediction ONTO the accumulated one (netR.compose: one transformation
         that samples where the two would in sequence) and warps the ORIGINAL real_A by the composite — one interpolation however many
         passes, the UNet STN's in the composing launch itself.  Afterwards netR.last_prediction() is the composite, registered_real_A and
         fake_RT_B are warps by it and fake_TR_B = netT(registered_real_A), so register() and registration_error() work unchanged.
-        cascade(1) is test().  Inference only: no autograd, no regularisation term for the further passes."""
+        cascade(1) is test().  Inference only: no autograd, no regularisation term for the further passes.
+        With regularity=True returns a list of `passes` (counts, stats) pairs: netR.regularity of the accumulated transformation after
+        each pass, at the network's size (composites are where folds appear); by default returns None, as before."""
         passes = int(passes)
         if passes < 1:
             raise ValueError('cascade: %d passes (at least 1)' % passes)
         self.test()
+        per_pass = [self.netR.regularity(self.netR.last_prediction())[:2]] if regularity else None
         if passes == 1:
-            return
+            return per_pass
         with torch.no_grad():
             acc = self.netR.last_prediction()
             dense = acc[1] == ops.GRID_UNET
@@ -227,13 +230,16 @@ class NEMARModel(BaseModel):
                     field = self.netR.compose(acc, new)
                     self.registered_real_A = self.netR.apply(field, [self.real_A])[0]
                 acc = (field, acc[1])
+                if regularity:
+                    per_pass.append(self.netR.regularity(acc)[:2])
             self.netR.set_last_prediction(acc[0])
             self.fake_RT_B = self.netR.apply(acc, [self.fake_B])[0]
             self.fake_TR_B = self.netT(self.registered_real_A)
             self.compute_visuals()
+        return per_pass
 
     def register(self, full_A, full_B=None, labels_A=None, translate=True, labels_B=None, landmarks_A=None, landmarks_B=None,
-                 num_classes=None):
+                 num_classes=None, regularity=False, jacobian_map=False):
         """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the
         network's resolution) predicted: the sampling grid is in normalised coordinates, so the prediction holds at every size, and the
         warp kernel resizes a dense field on the fly (ops.warp_resampled).  full_A [N,C,H,W] is modality A of the same N pairs at any
@@ -250,7 +256,12 @@ class NEMARModel(BaseModel):
         merely resampled to that size, K = num_classes or 1 + the largest id of the two maps (one host synchronisation); with
         landmarks_A and landmarks_B ([N,P,2] (x, y) in pixels of full_A and of the fixed image, which is full_B's size, or full_A's
         without full_B; NaN = missing) 'tre_px' and 'tre_before_px' [N,P]: |S(lm_B) - lm_A| with the prediction's S and with the
-        identity's, NaN where either point is missing."""
+        identity's, NaN where either point is missing.
+        With regularity=True (or jacobian_map=True, which implies it) 'jac_counts' int64 [N,2] and 'jac_stats' float32 [N,5]
+        (netR.regularity: interior pixels and folds; min, max and sum of the Jacobian determinant and the two log sums — sums, for
+        ops.regularity_summary) of the transformation at the fixed image's size — full_B's, or full_A's without full_B — and with
+        jacobian_map=True 'jacobian_det' [N,H,W], the determinant map there (NaN in the last row and column).  One more launch pair;
+        nothing else in the dict changes."""
         pred = self.netR.last_prediction()
         if pred is None:
             raise RuntimeError('register: no forward pass yet')
@@ -283,6 +294,11 @@ class NEMARModel(BaseModel):
                 out_hw = src_hw if full_B is None else tuple(full_B.shape[2:])
                 for key, (p, mode) in (('tre_px', pred), ('tre_before_px', identity)):
                     out[key] = (ops.map_points(p, mode, lm_B, src_hw, out_hw) - lm_A).norm(dim=2)
+            if regularity or jacobian_map:
+                fixed_hw = tuple(full_A.shape[2:]) if full_B is None else tuple(full_B.shape[2:])
+                out['jac_counts'], out['jac_stats'], det = self.netR.regularity(pred, fixed_hw, bool(jacobian_map))
+                if jacobian_map:
+                    out['jacobian_det'] = det
         return out
 
     def _netT_runs_at(self, h, w):

@@ -100,6 +100,12 @@ class AffineSTN(nn.Module):
         (ops.map_points).  No autograd."""
         return ops.map_points(prediction_tensor(field), ops.GRID_AFFINE, pts, src_hw, out_hw)
 
+    def regularity(self, field, out_hw=None, det_map=False):
+        """How regular the prediction's transformation is at out_hw (default: the network's size): (counts [N,2] = interior pixels and
+        folds, stats [N,5] = min / max / sum of the Jacobian determinant and the two log sums, the determinant map [N,Ho,Wo] or None) —
+        ops.jacobian_stats; an affine map has one determinant, theta's, at every pixel.  No autograd."""
+        return ops.jacobian_stats(prediction_tensor(field), ops.GRID_AFFINE, (self.net.h, self.net.w) if out_hw is None else out_hw, det_map)
+
     def compose(self, first, second):
         """ONE dtheta [N,6] that samples where `first` and then `second` would in sequence — an affine cascade stays affine, in closed
         form and exactly: under align_corners=False the base coordinate of the position S2(x) samples is theta2 applied to the base

@@ -155,6 +155,12 @@ class UnetSTN(nn.Module):
         (ops.map_points).  No autograd."""
         return ops.map_points(prediction_tensor(field), ops.GRID_UNET, pts, src_hw, out_hw)
 
+    def regularity(self, field, out_hw=None, det_map=False):
+        """How regular the prediction's transformation is at out_hw (default: the network's size): (counts [N,2] = interior pixels and
+        folds, stats [N,5] = min / max / sum of the Jacobian determinant and the two log sums, the determinant map [N,Ho,Wo] or None) —
+        ops.jacobian_stats; ops.regularity_summary turns counts and stats into fold share and SDlogJ.  No autograd."""
+        return ops.jacobian_stats(prediction_tensor(field), ops.GRID_UNET, (self.oh, self.ow) if out_hw is None else out_hw, det_map)
+
     def compose(self, first, second, image=None):
         """ONE prediction that samples where `first` and then `second` would in sequence — `second` was predicted from the pair `first`
         had already registered (a cascade pass), or `first` comes from an earlier run: the composite offsets [N,2,oh,ow] at the network's

@@ -14,6 +14,8 @@ import ctypes
 import os
 import weakref
 
+import numpy as np
+
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
@@ -1790,6 +1792,49 @@ def compose_predictions(first, first_mode, second, second_mode, out_hw, image=No
         warped = torch.empty_like(image)
     L.compose_pred(_p(first), first_mode, h1, w1, _p(second), second_mode, h2, w2, _p(field), _p(image), _p(warped), C, N, H, W, _stream())
     return field if image is None else (field, warped)
+
+
+JAC_COUNT_COLUMNS = ('interior', 'folds')
+JAC_STAT_COLUMNS = ('det_min', 'det_max', 'sum_det', 'sum_log_det', 'sum_log_det_sq')
+
+
+def jacobian_stats(pred, grid_mode, out_hw, det_map=False):
+    """How regular the transformation of a prediction is at out_hw = (Ho, Wo) (nemar_jacobian_stats): the forward-difference Jacobian
+    determinant of x -> p(x), p the position in pixels the warp samples in an image of the output's own size — exactly the grid
+    warp_resampled evaluates there — in one pass.  pred = offsets [N,2,hf,wf] (GRID_UNET) or dtheta [N,6] (GRID_AFFINE).  Returns
+    (counts int64 [N,2], columns JAC_COUNT_COLUMNS: pixels that have both forward neighbours, and those of them with det <= 0;
+    stats float32 [N,5], columns JAC_STAT_COLUMNS: min, max and sum over the interior pixels, the two log sums over those with det > 0;
+    det float32 [N,Ho,Wo] with NaN in the last row and column, or None without det_map) as device tensors: sums and counts, the caller
+    divides (regularity_summary).  counts and stats are the same bits with and without the map.  No autograd, no sync."""
+    pred, N, hf, wf = _prediction("jacobian_stats", pred, grid_mode)
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    counts = torch.empty((N, 2), dtype=torch.int32, device=pred.device)
+    stats = torch.empty((N, 5), dtype=torch.float32, device=pred.device)
+    det = torch.empty((N, Ho, Wo), dtype=torch.float32, device=pred.device) if det_map else None
+    wsb = Q.jacobian_stats_workspace(N, Ho, Wo)
+    ws = _workspace(wsb, pred.device)
+    L.jacobian_stats(_p(pred), grid_mode, _p(det), _p(counts), _p(stats), _p(ws), wsb, N, hf, wf, Ho, Wo, _stream())
+    return counts.to(torch.int64), stats, det            # (uint32 counts below 2^31: the int32 view holds them)
+
+
+def regularity_summary(counts, stats):
+    """What the literature reports next to Dice and landmark error, from jacobian_stats' counts [M,2] and stats [M,5] of any number of
+    samples (tensors or arrays; the batches concatenated along the first axis), on the host in float64: interior and folds (ints),
+    fold_frac = folds / interior, det_min, det_max, det_mean, and over the pixels with det > 0 log_det_mean and log_det_std — SDlogJ,
+    sqrt(sum2 / k - (sum1 / k)^2) from the two sums.  Counts and sums are added over the samples, then divided; None where there is no
+    pixel to average."""
+    host = lambda a, dt: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(dt).reshape(-1, a.shape[-1])
+    c, s = host(counts, np.int64), host(stats, np.float64)
+    interior, folds = int(c[:, 0].sum()), int(c[:, 1].sum())
+    out = {'interior': interior, 'folds': folds, 'fold_frac': None, 'det_min': None, 'det_max': None, 'det_mean': None,
+           'log_det_mean': None, 'log_det_std': None}
+    if interior > 0:
+        out.update(fold_frac=folds / interior, det_min=float(s[:, 0].min()), det_max=float(s[:, 1].max()), det_mean=float(s[:, 2].sum()) / interior)
+    k = interior - folds
+    if k > 0:
+        mean = float(s[:, 3].sum()) / k
+        out.update(log_det_mean=mean, log_det_std=float(np.sqrt(max(float(s[:, 4].sum()) / k - mean * mean, 0.0))))
+    return out
 
 
 # ---- known misalignment: ground-truth fields, the deforming input pipeline, the registration-error meter (no autograd: data and read-outs) ----

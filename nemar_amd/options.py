@@ -134,5 +134,9 @@ class TestOptions(BaseOptions):
         a('--num_test', type=int, default=50)
         # (MI355X build) python -m nemar_amd.register: looks at every pair, each from the pair the previous ones registered (NEMARModel.cascade)
         a('--passes', type=int, default=1)
+        # python -m nemar_amd.register: regularity.json (folds, SDlogJ: NEMARModel.register(regularity=True)); --jacobian_map implies it and
+        # also writes the determinant map, jacobian_det.npy
+        a('--regularity', action='store_true')
+        a('--jacobian_map', action='store_true')
         self.isTrain = False
         return parser

@@ -22,7 +22,14 @@ Written under --results_dir/--name/:
                               Dice before and after registration, from the counts of the whole data set; mean, median and max
                               distance in pixels between the mapped landmarks of B and those of A, before and after, and how many
                               point pairs were used
-and one summary line on stdout: pairs, sizes, the scores, seconds."""
+    regularity.json           only with --regularity: how regular the transformation is at the images' native size (B.npy's), from the
+                              counts and sums of the whole data set (ops.regularity_summary): interior pixels, folds (Jacobian
+                              determinant <= 0) and their share, min / max / mean determinant, mean and standard deviation of the
+                              log-determinant over the pixels that do not fold (SDlogJ); with --passes K > 1 also `per_pass`, K such
+                              summaries of the accumulated transformation after each pass, at the network's size
+    jacobian_det.npy          only with --jacobian_map (which implies --regularity): the determinant map [M,H,W] float32 at B.npy's
+                              size, NaN in the last row and column (csrc/regularity.hip)
+and one summary line on stdout: pairs, sizes, the scores (with --regularity: folds in per cent and SDlogJ), seconds."""
 import json
 import os
 import time
@@ -32,6 +39,7 @@ import torch
 
 from .data.gpupairs_dataset import GpuPairsDataset
 from .models import create_model
+from . import ops
 from .options import TestOptions
 
 def network_batch(pool_A, pool_B, indices, opt):
@@ -132,14 +140,25 @@ def main(argv=None):
     model.setup(opt)
     if opt.eval:
         model.eval()
+    want_reg = bool(opt.regularity or opt.jacobian_map)
+    jac = {k: [] for k in ('jac_counts', 'jac_stats', 'jacobian_det')}
+    per_pass = [[] for _ in range(opt.passes)] if want_reg and opt.passes > 1 else []
     reg, reg_labels, offsets = [], [], []
     for i0 in range(0, M, opt.batch_size):
         idx = list(range(i0, min(M, i0 + opt.batch_size)))
         model.set_input(network_batch(pool_A, pool_B, idx, opt))
-        model.cascade(opt.passes)
+        if want_reg:
+            for k, pair in zip(per_pass, model.cascade(opt.passes, regularity=True)):
+                k.append(pair)
+        else:
+            model.cascade(opt.passes)
         part = lambda t: None if t is None else t[idx[0]:idx[-1] + 1]
         out = model.register(part(pool_A), part(pool_B), part(labels), translate=False,          # (fake_RT_B is not among the files this command writes)
-                             labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes)
+                             labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes,
+                             **(dict(regularity=True, jacobian_map=opt.jacobian_map) if want_reg else {}))
+        for k in jac:
+            if k in out:
+                jac[k].append(out[k])
         for k in scored:
             if k in out:
                 scored[k].append(out[k])
@@ -163,6 +182,17 @@ def main(argv=None):
             told += ', mean Dice %.4f -> %.4f over %d classes' % (scores['dice']['mean_before'], scores['dice']['mean_after'], len(scores['dice']['classes']))
         if scores.get('tre_px', {}).get('points'):
             told += ', mean TRE %.3f -> %.3f px over %d points' % (scores['tre_px']['before']['mean'], scores['tre_px']['after']['mean'], scores['tre_px']['points'])
+    if want_reg:
+        regularity = ops.regularity_summary(torch.cat(jac['jac_counts']), torch.cat(jac['jac_stats']))
+        if per_pass:
+            regularity['per_pass'] = [ops.regularity_summary(torch.cat([c for c, _ in k]), torch.cat([s for _, s in k])) for k in per_pass]
+        with open(os.path.join(out_dir, 'regularity.json'), 'w') as f:
+            json.dump(regularity, f, indent=1)
+        if opt.jacobian_map:
+            np.save(os.path.join(out_dir, 'jacobian_det.npy'), torch.cat(jac['jacobian_det']).cpu().numpy())
+        if regularity['fold_frac'] is not None:
+            told += ', folds %.2f %%, SDlogJ %s' % (100.0 * regularity['fold_frac'],
+                                                   'n/a' if regularity['log_det_std'] is None else '%.3f' % regularity['log_det_std'])
     torch.cuda.synchronize()
     print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s%s, %.2f s -> %s'
           % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width, '' if opt.passes == 1 else ' in %d passes' % opt.passes,
