@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 608 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 609 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -546,6 +546,32 @@ int nemar_compose_pred(const float* first, int first_mode, int h1, int w1, const
 size_t nemar_jacobian_stats_workspace(int N, int Ho, int Wo);
 int nemar_jacobian_stats(const float* pred, int grid_mode, float* det_out, unsigned* counts, float* stats, void* workspace,
                          size_t ws_bytes, int N, int hf, int wf, int Ho, int Wo, void* stream);
+
+/* Intensity agreement of a registration (csrc/similarity.hip; not in the reference, which has no evaluation code): a score that needs
+ * no annotation — the joint histogram of the registered moving image and the fixed image (mutual information, across modalities) and
+ * the moments behind NCC / MSE / MAE (within one modality), in one pass over the output.  pred, grid_mode, hf and wf are what
+ * nemar_warp_resampled_fwd takes (NEMAR_GRID_UNET offsets [N,2,hf,wf], resized in registers; NEMAR_GRID_AFFINE dtheta [N,6], hf and wf
+ * ignored; NEMAR_GRID_EXPLICIT is NEMAR_EINVAL).  moving [N,Cm,Hs,Ws] (any size), fixed [N,Cf,Ho,Wo].  For output pixel x:
+ *   a(x) = (sum over the Cm channels, ascending, of the value nemar_warp_resampled_fwd(..., NEMAR_SAMPLE_BILINEAR) would write there —
+ *          the same code computes it; the warped image is never written to memory) * (1.f / Cm);
+ *   b(x) = (sum over the Cf channels, ascending, of fixed(x)) * (1.f / Cf).
+ * x COUNTS iff the nearest texel of its sampling position lies inside the source (the pixels where nemar_label_overlap's warped map is
+ * not padding: an identity prediction at equal sizes counts every pixel) and neither a(x) nor b(x) is NaN.
+ *   bin(v) = clamp((int)floorf((v - lo) * (bins / (hi - lo))), 0, bins - 1) per side: values outside [lo, hi] go to the end bins.
+ * counts [N,bins,bins] uint32 is OVERWRITTEN (cleared on `stream` by the entry point): counts[n][bin(a)][bin(b)] over the counted pixels.
+ * Its sum is the number of counted pixels, its row and column sums the marginals.  Integers added with integer atomics: order
+ * independent, bitwise repeatable.
+ * moments [N,6] or NULL: sum a, sum b, sum a^2, sum b^2, sum ab, sum |a - b| over the counted pixels (NCC, MSE, MAE are the caller's
+ * arithmetic, in double).  Per-workgroup records go to the workspace and are merged in a fixed order: no atomics, bitwise repeatable.
+ * With moments == NULL no workspace is needed (workspace and ws_bytes are ignored) and counts holds the same bits.
+ * NEMAR_EINVAL, nothing launched: moving, fixed, pred or counts NULL; moments without a workspace; any pointer in use not 4-byte
+ * aligned (that is all the alignment asked for); a grid_mode other than NEMAR_GRID_UNET / NEMAR_GRID_AFFINE; bins outside 2 .. 64; Cm or
+ * Cf outside 1 .. 64; hi <= lo on either side (or a range without a finite bin width); a non-positive size; hf or wf < 1 with
+ * NEMAR_GRID_UNET; N > 65535; Ho*Wo or Hs*Ws >= 2^31 (a field plane >= 2^30); with moments, ws_bytes < nemar_joint_histogram_workspace(). */
+size_t nemar_joint_histogram_workspace(int N, int Ho, int Wo);
+int nemar_joint_histogram(const float* moving, const float* fixed, const float* pred, int grid_mode, unsigned* counts, float* moments,
+                          void* workspace, size_t ws_bytes, int N, int Cm, int Cf, int bins, float lo_m, float hi_m, float lo_f,
+                          float hi_f, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

@@ -55,7 +55,9 @@ extern "C" {
  *   44 nemar_warp_resampled_fwd: 4 consecutive pixels per lane and 16-byte stores where Wo % 4 == 0 and out is 16-byte aligned (1) / one pixel
  *      per lane everywhere (0, default: the 16-byte form takes 27 - 37 % longer, profiles/register_fullres.txt)
  *   45 nemar_label_overlap: every lane adds to the workgroup's LDS histogram for itself (1) / the lanes that share the wave's first key are
- *      added once, by a ballot (0, default; tools/profiles/label_overlap.txt) */
+ *      added once, by a ballot (0, default; tools/profiles/label_overlap.txt)
+ *   46 nemar_joint_histogram: every lane adds to the workgroup's LDS table for itself (1, default) / the lanes that share the wave's first
+ *      cell are added once, by a ballot (0: 0 - 3 % slower at 2048^2, tools/profiles/joint_histogram.txt) */
 int nemar_tune(int key, int value);
 int nemar_tune_ptr(void* timeline_buffer);   /* device buffer for per-stage cycle stamps (tools/timeline_*.py), NULL = off */
 /* grad_input variant for A/B measurements: 0 (default) = gather + fixed point (needs the workspace), 1 = fp32 atomics through an

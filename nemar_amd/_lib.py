@@ -105,6 +105,8 @@ SIGNATURES = {
     "nemar_compose_pred": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nemar_jacobian_stats_workspace": (_sz, [_i, _i, _i]),
     "nemar_jacobian_stats": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
+    "nemar_joint_histogram_workspace": (_sz, [_i, _i, _i]),
+    "nemar_joint_histogram": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_dropout": (_i, [_vp, _vp, _ll, _fl, _u64, _u32, _vp]),
     "nemar_dropout_max": (_i, [_vp, _vp, _i, _ll, _fl, _u64, _u32, _vp, _vp]),
     "nemar_loss_workspace": (_sz, []),

@@ -22,6 +22,7 @@ extern int g_narrow_fwd4;                        // conv_narrow.hip
 extern int g_wg_xreg;                            // conv_split16_wgrad.hip
 extern int g_register_vec4;                      // register.hip
 extern int g_overlap_per_lane;                   // score.hip
+extern int g_histogram_per_lane;                 // similarity.hip
 void nemar_norm_planes_debug(int bits);          // norm_planes.hip: ablation bits of the fused producer (measurement only)
 #endif
 
@@ -973,6 +974,7 @@ NEMAR_API int nemar_tune(int key, int value) {
     if (key == 38) { g_wg_xreg = value != 0; return NEMAR_OK; }   // wide 3x3 weight gradient: X pieces through registers
     if (key == 39) { g_split16_ksplit_cap = value < 1 ? 1 : (value > 8 ? 8 : value); return NEMAR_OK; }      // most reduction runs per tile of the wide-layer kernel
     if (key == 45) { g_overlap_per_lane = value != 0; return NEMAR_OK; }  // nemar_label_overlap: every lane adds to the LDS histogram itself (1) / wave-aggregated adds (0, default)
+    if (key == 46) { g_histogram_per_lane = value != 0; return NEMAR_OK; }  // nemar_joint_histogram: every lane adds to the LDS table itself (1, default) / wave-aggregated adds (0)
     if (key == 44) { g_register_vec4 = value != 0; return NEMAR_OK; }   // nemar_warp_resampled_fwd: 4 pixels per lane + 16-byte stores (1) / one pixel per lane (0, default)
     if (key == 35) { g_dual_gy = value != 0; return NEMAR_OK; }
     if (key == 34) { nemar_split16_wgrad_tune(value); return NEMAR_OK; }      // wide weight gradient: 1 one gy copy (default), 0 KS shifted copies

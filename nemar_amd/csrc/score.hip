@@ -19,6 +19,7 @@
 // (nemar_tune(45, 1), measurement build) on blocky, single-class and per-pixel-random maps: tools/profiles/label_overlap.txt.
 #include "common.h"
 #include "resampled_grid.h"
+#include "wave_count.h"
 
 namespace {
 
@@ -29,25 +30,6 @@ __device__ __forceinline__ int class_of(float v, int K) {
     if (!(v >= 0.f && v < (float)K)) return -1;
     const int k = (int)v;
     return (float)k == v ? k : -1;
-}
-
-// hist[key] += 1 from every lane with key >= 0 (the whole wave calls this together): the lanes that hold the first counting lane's key
-// are added by that lane alone.  per_lane (a launch argument, 0 in the product: the same kernel in both builds of the library): every
-// lane adds for itself
-__device__ __forceinline__ void wave_count(unsigned* hist, int key, int per_lane) {
-    const bool counts = key >= 0;
-    if (per_lane) {                                               // (wave-uniform)
-        if (counts) atomicAdd(&hist[key], 1u);
-        return;
-    }
-    const unsigned long long active = __ballot(counts);
-    if (active == 0ull) return;                                   // (wave-uniform)
-    const int leader = __builtin_ctzll(active);
-    const int lead_key = __shfl(key, leader, 64);
-    const unsigned long long same = __ballot(counts && key == lead_key);
-    const int lane = threadIdx.x & 63;
-    if (lane == leader) atomicAdd(&hist[lead_key], (unsigned)__builtin_popcountll(same));
-    else if (counts && key != lead_key) atomicAdd(&hist[key], 1u);
 }
 
 // KCAP: the histogram's capacity in classes (K <= KCAP) — 256 (3 KiB + the 9.3 KiB patch: eight workgroups fit a CU's LDS) or 1024

@@ -202,7 +202,7 @@ class NEMARModel(BaseModel):
         cols[2] = rows[:, 2].max()
         return registration_summary(cols.tolist(), self.gt_field.size(0) * self.gt_field.size(2) * self.gt_field.size(3))
 
-    def cascade(self, passes, regularity=False):
+    def cascade(self, passes, regularity=False, similarity=False, bins=32):
         """test() with `passes` looks at the set_input pair (a "recursive cascade"): pass 1 is test() exactly as it is; every further pass
         predicts from (registered_real_A, real_B), composes that prediction ONTO the accumulated one (netR.compose: one transformation
         that samples where the two would in sequence) and warps the ORIGINAL real_A by the composite — one interpolation however many
@@ -210,14 +210,19 @@ class NEMARModel(BaseModel):
         fake_RT_B are warps by it and fake_TR_B = netT(registered_real_A), so register() and registration_error() work unchanged.
         cascade(1) is test().  Inference only: no autograd, no regularisation term for the further passes.
         With regularity=True returns a list of `passes` (counts, stats) pairs: netR.regularity of the accumulated transformation after
-        each pass, at the network's size (composites are where folds appear); by default returns None, as before."""
+        each pass, at the network's size (composites are where folds appear); by default returns None, as before.
+        With similarity=True returns a list of `passes` (counts, moments) pairs: netR.similarity of real_A under the accumulated
+        transformation against real_B after each pass, at the network's size, `bins` bins over [-1, 1] (ops.similarity_summary turns a
+        pair into mutual information and NCC).  With both flags: {'regularity': [...], 'similarity': [...]}."""
         passes = int(passes)
         if passes < 1:
             raise ValueError('cascade: %d passes (at least 1)' % passes)
         self.test()
         per_pass = [self.netR.regularity(self.netR.last_prediction())[:2]] if regularity else None
+        agreement = [self.netR.similarity(self.netR.last_prediction(), self.real_A, self.real_B, bins)] if similarity else None
+        told = {'regularity': per_pass, 'similarity': agreement} if regularity and similarity else (agreement if similarity else per_pass)
         if passes == 1:
-            return per_pass
+            return told
         with torch.no_grad():
             acc = self.netR.last_prediction()
             dense = acc[1] == ops.GRID_UNET
@@ -232,14 +237,16 @@ class NEMARModel(BaseModel):
                 acc = (field, acc[1])
                 if regularity:
                     per_pass.append(self.netR.regularity(acc)[:2])
+                if similarity:
+                    agreement.append(self.netR.similarity(acc, self.real_A, self.real_B, bins))
             self.netR.set_last_prediction(acc[0])
             self.fake_RT_B = self.netR.apply(acc, [self.fake_B])[0]
             self.fake_TR_B = self.netT(self.registered_real_A)
             self.compute_visuals()
-        return per_pass
+        return told
 
     def register(self, full_A, full_B=None, labels_A=None, translate=True, labels_B=None, landmarks_A=None, landmarks_B=None,
-                 num_classes=None, regularity=False, jacobian_map=False):
+                 num_classes=None, regularity=False, jacobian_map=False, similarity=False, bins=32, intensity_range=(-1., 1.)):
         """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the
         network's resolution) predicted: the sampling grid is in normalised coordinates, so the prediction holds at every size, and the
         warp kernel resizes a dense field on the fly (ops.warp_resampled).  full_A [N,C,H,W] is modality A of the same N pairs at any
@@ -261,6 +268,11 @@ class NEMARModel(BaseModel):
         (netR.regularity: interior pixels and folds; min, max and sum of the Jacobian determinant and the two log sums — sums, for
         ops.regularity_summary) of the transformation at the fixed image's size — full_B's, or full_A's without full_B — and with
         jacobian_map=True 'jacobian_det' [N,H,W], the determinant map there (NaN in the last row and column).  One more launch pair;
+        nothing else in the dict changes.
+        With similarity=True (full_B is needed, and is read) 'similarity' = {'before': (counts, moments), 'after': (counts, moments)}:
+        netR.similarity of full_A against full_B at full_B's size — the joint histogram int64 [N,bins,bins] of the two channel means
+        over intensity_range (the value range of the images handed in) and the moments float32 [N,6] — under the identity and under
+        the prediction (ops.similarity_summary: mutual information, NCC, MSE, MAE).  No annotation is needed.  Two more launch pairs;
         nothing else in the dict changes."""
         pred = self.netR.last_prediction()
         if pred is None:
@@ -299,6 +311,13 @@ class NEMARModel(BaseModel):
                 out['jac_counts'], out['jac_stats'], det = self.netR.regularity(pred, fixed_hw, bool(jacobian_map))
                 if jacobian_map:
                     out['jacobian_det'] = det
+            if similarity:
+                if full_B is None:
+                    raise ValueError('register: similarity=True needs full_B, the fixed images')
+                full_B = full_B.to(self.device, dtype=torch.float32).contiguous()
+                zeros = torch.zeros((pred[0].size(0), 6), dtype=torch.float32, device=self.device)
+                out['similarity'] = {'before': ops.joint_histogram(zeros, ops.GRID_AFFINE, full_A, full_B, bins, intensity_range, intensity_range),
+                                     'after': self.netR.similarity(pred, full_A, full_B, bins, intensity_range, intensity_range)}
         return out
 
     def _netT_runs_at(self, h, w):

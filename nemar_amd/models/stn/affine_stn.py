@@ -106,6 +106,12 @@ class AffineSTN(nn.Module):
         ops.jacobian_stats; an affine map has one determinant, theta's, at every pixel.  No autograd."""
         return ops.jacobian_stats(prediction_tensor(field), ops.GRID_AFFINE, (self.net.h, self.net.w) if out_hw is None else out_hw, det_map)
 
+    def similarity(self, field, moving, fixed, bins=32, range_moving=(-1., 1.), range_fixed=(-1., 1.), moments=True):
+        """Intensity agreement of `moving` warped by the prediction — what apply() gives, never written — with `fixed` at its size:
+        (counts [N,bins,bins], the joint histogram of the two channel means; moments [N,6] or None) — ops.joint_histogram;
+        ops.similarity_summary turns them into mutual information, NCC, MSE and MAE.  Needs no annotation.  No autograd."""
+        return ops.joint_histogram(prediction_tensor(field), ops.GRID_AFFINE, moving, fixed, bins, range_moving, range_fixed, moments)
+
     def compose(self, first, second):
         """ONE dtheta [N,6] that samples where `first` and then `second` would in sequence — an affine cascade stays affine, in closed
         form and exactly: under align_corners=False the base coordinate of the position S2(x) samples is theta2 applied to the base

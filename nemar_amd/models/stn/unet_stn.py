@@ -161,6 +161,12 @@ class UnetSTN(nn.Module):
         ops.jacobian_stats; ops.regularity_summary turns counts and stats into fold share and SDlogJ.  No autograd."""
         return ops.jacobian_stats(prediction_tensor(field), ops.GRID_UNET, (self.oh, self.ow) if out_hw is None else out_hw, det_map)
 
+    def similarity(self, field, moving, fixed, bins=32, range_moving=(-1., 1.), range_fixed=(-1., 1.), moments=True):
+        """Intensity agreement of `moving` warped by the prediction — what apply() gives, never written — with `fixed` at its size:
+        (counts [N,bins,bins], the joint histogram of the two channel means; moments [N,6] or None) — ops.joint_histogram;
+        ops.similarity_summary turns them into mutual information, NCC, MSE and MAE.  Needs no annotation.  No autograd."""
+        return ops.joint_histogram(prediction_tensor(field), ops.GRID_UNET, moving, fixed, bins, range_moving, range_fixed, moments)
+
     def compose(self, first, second, image=None):
         """ONE prediction that samples where `first` and then `second` would in sequence — `second` was predicted from the pair `first`
         had already registered (a cascade pass), or `first` comes from an earlier run: the composite offsets [N,2,oh,ow] at the network's

@@ -1837,6 +1837,74 @@ def regularity_summary(counts, stats):
     return out
 
 
+MOMENT_COLUMNS = ('sum_a', 'sum_b', 'sum_aa', 'sum_bb', 'sum_ab', 'sum_abs_diff')
+MAX_HISTOGRAM_BINS = 64
+
+
+def joint_histogram(pred, grid_mode, moving, fixed, bins=32, range_moving=(-1., 1.), range_fixed=(-1., 1.), moments=True):
+    """Intensity agreement of a registration, no annotation needed (nemar_joint_histogram): moving [N,Cm,Hs,Ws] warped bilinearly by the
+    prediction — exactly what warp_resampled returns, but never written — against fixed [N,Cf,Ho,Wo] at its size, channels averaged on
+    both sides.  Returns (counts int64 [N,bins,bins]: the joint histogram, moving bin = row, fixed bin = column, values outside a range
+    in its end bins; moments float32 [N,6], columns MOMENT_COLUMNS, or None with moments=False) as device tensors: counts and sums, the
+    caller divides (similarity_summary).  A pixel counts where the nearest texel of its sampling position is inside the source and
+    neither value is NaN.  An identity prediction (GRID_AFFINE, zeros [N,6]) gives the agreement before registration.  counts are the
+    same bits with and without the moments.  No autograd, no sync."""
+    pred, N, hf, wf = _prediction("joint_histogram", pred, grid_mode)
+    imgs = []
+    for name, img in (("moving", moving), ("fixed", fixed)):
+        img = img.detach()
+        if img.dim() != 4 or img.shape[0] != N or not 1 <= img.shape[1] <= 64:
+            raise ValueError("joint_histogram: %s image %s, expected [N,C,H,W] with N = %d and 1 <= C <= 64" % (name, tuple(img.shape), N))
+        imgs.append(_c(img.to(torch.float32)))
+    B = int(bins)
+    if not 2 <= B <= MAX_HISTOGRAM_BINS:
+        raise ValueError("joint_histogram: %d bins (2 .. %d)" % (B, MAX_HISTOGRAM_BINS))
+    (lo_m, hi_m), (lo_f, hi_f) = ((float(r[0]), float(r[1])) for r in (range_moving, range_fixed))
+    if not (hi_m > lo_m and hi_f > lo_f):
+        raise ValueError("joint_histogram: empty range %r or %r" % (tuple(range_moving), tuple(range_fixed)))
+    m, f = imgs
+    Ho, Wo = int(f.shape[2]), int(f.shape[3])
+    counts = torch.empty((N, B, B), dtype=torch.int32, device=f.device)
+    mom = ws = None
+    wsb = 0
+    if moments:
+        mom = torch.empty((N, 6), dtype=torch.float32, device=f.device)
+        wsb = Q.joint_histogram_workspace(N, Ho, Wo)
+        ws = _workspace(wsb, f.device)
+    L.joint_histogram(_p(m), _p(f), _p(pred), grid_mode, _p(counts), _p(mom), _p(ws), wsb, N, int(m.shape[1]), int(f.shape[1]), B,
+                      lo_m, hi_m, lo_f, hi_f, int(m.shape[2]), int(m.shape[3]), hf, wf, Ho, Wo, _stream())
+    return counts.to(torch.int64), mom                     # (uint32 counts below 2^31: the int32 view holds them)
+
+
+def similarity_summary(counts, moments=None):
+    """What is reported for a registration without annotations, from joint_histogram's counts [M,B,B] and moments [M,6] of any number of
+    samples (tensors or arrays; the batches concatenated along the first axis), on the host in float64.  Tables and sums are added over
+    the samples first, then divided.  From the table: valid (int, the counted pixels), entropy_moving, entropy_fixed, entropy_joint and
+    mi = H_m + H_f - H_joint in nats, nmi = (H_m + H_f) / H_joint.  From the moments, where given: ncc (Pearson correlation of the two
+    intensities), mse, mae.  None where there is nothing to divide by: no counted pixel, zero joint entropy (nmi), zero variance (ncc)."""
+    host = lambda a, dt: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(dt)
+    c = host(counts, np.int64)
+    table = c.reshape(-1, c.shape[-2], c.shape[-1]).sum(0)
+    valid = int(table.sum())
+    out = {'valid': valid, 'entropy_moving': None, 'entropy_fixed': None, 'entropy_joint': None, 'mi': None, 'nmi': None}
+    if valid > 0:
+        def entropy(k):
+            p = k[k > 0].astype(np.float64) / valid
+            return float(-(p * np.log(p)).sum())
+        h_m, h_f, h_j = entropy(table.sum(1)), entropy(table.sum(0)), entropy(table.ravel())
+        out.update(entropy_moving=h_m, entropy_fixed=h_f, entropy_joint=h_j, mi=h_m + h_f - h_j, nmi=(h_m + h_f) / h_j if h_j > 0 else None)
+    if moments is not None:
+        s = host(moments, np.float64).reshape(-1, 6).sum(0)
+        out.update(ncc=None, mse=None, mae=None)
+        if valid > 0:
+            sa, sb, saa, sbb, sab, sad = (float(v) for v in s)
+            var_a, var_b, cov = saa / valid - (sa / valid) ** 2, sbb / valid - (sb / valid) ** 2, sab / valid - (sa / valid) * (sb / valid)
+            out.update(mse=(saa - 2.0 * sab + sbb) / valid, mae=sad / valid, ncc=cov / np.sqrt(var_a * var_b) if var_a > 0 and var_b > 0 else None)
+            if out['ncc'] is not None:
+                out['ncc'] = float(out['ncc'])
+    return out
+
+
 # ---- known misalignment: ground-truth fields, the deforming input pipeline, the registration-error meter (no autograd: data and read-outs) ----
 def deform_field(params, B, Hc, Wc, gh, gw):
     """params [B, 6 + 2*gh*gw] (a11 a12 tx a21 a22 ty about the crop centre, then a [2,gh,gw] lattice of pixel displacements; gh = gw = 0:

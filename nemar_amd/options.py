@@ -138,5 +138,9 @@ class TestOptions(BaseOptions):
         # also writes the determinant map, jacobian_det.npy
         a('--regularity', action='store_true')
         a('--jacobian_map', action='store_true')
+        # python -m nemar_amd.register: similarity.json (mutual information, NCC, MSE, MAE of the pair before and after registration, from
+        # A.npy / B.npy alone: NEMARModel.register(similarity=True)); --bins: the joint histogram's bins per side (2 .. 64)
+        a('--similarity', action='store_true')
+        a('--bins', type=int, default=32)
         self.isTrain = False
         return parser

@@ -29,7 +29,14 @@ Written under --results_dir/--name/:
                               summaries of the accumulated transformation after each pass, at the network's size
     jacobian_det.npy          only with --jacobian_map (which implies --regularity): the determinant map [M,H,W] float32 at B.npy's
                               size, NaN in the last row and column (csrc/regularity.hip)
-and one summary line on stdout: pairs, sizes, the scores (with --regularity: folds in per cent and SDlogJ), seconds."""
+    similarity.json           only with --similarity: how well the intensities of A.npy agree with B.npy's at B.npy's size, `before`
+                              (A merely resampled) and `after` registration, from the tables and sums of the whole data set
+                              (ops.similarity_summary): counted pixels, the entropies, mutual information (nats) and its normalised
+                              form from a --bins x --bins joint histogram of the channel means over [0, 1]; NCC, MSE and MAE; with
+                              --passes K > 1 also `per_pass`, K such summaries of the network-size pair after each pass.  Needs no
+                              annotation: A.npy and B.npy are enough (csrc/similarity.hip)
+and one summary line on stdout: pairs, sizes, the scores (with --regularity: folds in per cent and SDlogJ; with --similarity:
+MI before -> after), seconds."""
 import json
 import os
 import time
@@ -143,19 +150,29 @@ def main(argv=None):
     want_reg = bool(opt.regularity or opt.jacobian_map)
     jac = {k: [] for k in ('jac_counts', 'jac_stats', 'jacobian_det')}
     per_pass = [[] for _ in range(opt.passes)] if want_reg and opt.passes > 1 else []
+    sim = {'before': [], 'after': []}
+    sim_per_pass = [[] for _ in range(opt.passes)] if opt.similarity and opt.passes > 1 else []
     reg, reg_labels, offsets = [], [], []
     for i0 in range(0, M, opt.batch_size):
         idx = list(range(i0, min(M, i0 + opt.batch_size)))
         model.set_input(network_batch(pool_A, pool_B, idx, opt))
-        if want_reg:
-            for k, pair in zip(per_pass, model.cascade(opt.passes, regularity=True)):
-                k.append(pair)
+        told_passes = model.cascade(opt.passes, regularity=want_reg, similarity=opt.similarity, bins=opt.bins)
+        if want_reg and opt.similarity:
+            reg_passes, sim_passes = told_passes['regularity'], told_passes['similarity']
         else:
-            model.cascade(opt.passes)
+            reg_passes, sim_passes = (told_passes, []) if want_reg else ([], told_passes or [])
+        for k, pair in zip(per_pass, reg_passes):
+            k.append(pair)
+        for k, pair in zip(sim_per_pass, sim_passes):
+            k.append(pair)
         part = lambda t: None if t is None else t[idx[0]:idx[-1] + 1]
         out = model.register(part(pool_A), part(pool_B), part(labels), translate=False,          # (fake_RT_B is not among the files this command writes)
                              labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes,
-                             **(dict(regularity=True, jacobian_map=opt.jacobian_map) if want_reg else {}))
+                             **(dict(regularity=True, jacobian_map=opt.jacobian_map) if want_reg else {}),
+                             **(dict(similarity=True, bins=opt.bins, intensity_range=(0.0, 1.0)) if opt.similarity else {}))
+        for k in sim:
+            if 'similarity' in out:
+                sim[k].append(out['similarity'][k])
         for k in jac:
             if k in out:
                 jac[k].append(out[k])
@@ -193,6 +210,15 @@ def main(argv=None):
         if regularity['fold_frac'] is not None:
             told += ', folds %.2f %%, SDlogJ %s' % (100.0 * regularity['fold_frac'],
                                                    'n/a' if regularity['log_det_std'] is None else '%.3f' % regularity['log_det_std'])
+    if opt.similarity:
+        whole = lambda pairs: ops.similarity_summary(torch.cat([c for c, _ in pairs]), torch.cat([m for _, m in pairs]))
+        similarity = {k: whole(v) for k, v in sim.items()}
+        if sim_per_pass:
+            similarity['per_pass'] = [whole(k) for k in sim_per_pass]
+        with open(os.path.join(out_dir, 'similarity.json'), 'w') as f:
+            json.dump(similarity, f, indent=1)
+        if similarity['after']['mi'] is not None and similarity['before']['mi'] is not None:
+            told += ', MI %.4f -> %.4f' % (similarity['before']['mi'], similarity['after']['mi'])
     torch.cuda.synchronize()
     print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s%s, %.2f s -> %s'
           % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width, '' if opt.passes == 1 else ' in %d passes' % opt.passes,
