@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 609 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 610 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -90,6 +90,33 @@ int nemar_smoothness_fwd(const float* d, const float* img, int Ci, float alpha, 
                          int N, int H, int W, void* stream);
 int nemar_smoothness_bwd(const float* d, const float* img, int Ci, float alpha, const float* gscale,
                          float factor, float* gd, int accumulate, int N, int H, int W, void* stream);
+
+/* Fold penalty (csrc/fold.hip; not in the reference, whose only regulariser is the smoothness term above): a hinge on the Jacobian
+ * determinant nemar_jacobian_stats measures, as a differentiable loss on a UNet offset field.  d [N,2,H,W], channel 0 = x, taken at the
+ * size the warp reads it (NEMAR_GRID_UNET).  For pixel (h,w):
+ *   g   = (linspace(-1,1,W)[w] + d[n,0,h,w], linspace(-1,1,H)[h] + d[n,1,h,w])        the warp's normalised coordinate (the same bits)
+ *   p   = ((g.x + 1) * W - 1) / 2, ((g.y + 1) * H - 1) / 2                             the position it samples, in pixels
+ *   a   = p(h,w+1) - p(h,w),  b = p(h+1,w) - p(h,w),  det = a.x * b.y - b.x * a.y      the bits nemar_jacobian_stats computes with
+ *                                                                                      NEMAR_GRID_UNET at hf = Ho = H, wf = Wo = W
+ *   interior = h < H-1 and w < W-1;  M = N (H-1) (W-1).
+ * fwd: loss[0] = (accumulate ? loss[0] : 0) + factor / M * sum over the interior pixels of max(0, margin - det);
+ *      active [N] uint32: active[n] = #(interior pixels of sample n with det <= margin) — with margin = 0, nemar_jacobian_stats' fold count.
+ *      M = 0 (H == 1 or W == 1): the sum is 0 and active = 0, both WRITTEN.  Per-workgroup records (one per 64 x 16 tile) go to the
+ *      workspace and are merged in a fixed order: no atomics, bitwise repeatable.
+ * bwd: gd [N,2,H,W] (+)= gscale[0] * d loss / d d (gscale: device scalar, the upstream gradient).  The hinge has slope -1 where
+ *      det < margin and 0 elsewhere, equality included (torch's relu).  With s(h,w) = -gscale[0] * factor / M on such interior pixels, 0 elsewhere:
+ *        gd[n,0,h,w] = (W/2) * [ s(h,w) * (a.y - b.y)(h,w) + s(h,w-1) * b.y(h,w-1) + s(h-1,w) * (-a.y)(h-1,w) ]
+ *        gd[n,1,h,w] = (H/2) * [ s(h,w) * (b.x - a.x)(h,w) + s(h,w-1) * (-b.x)(h,w-1) + s(h-1,w) * a.x(h-1,w) ]
+ *      — the texel as p(h,w) of its own pixel, as p(h,w+1) of the left one, as p(h+1,w) of the upper one; a term whose pixel does not
+ *      exist or is not interior is absent; the three are added in this order.  M = 0: all zeros, written.  A gather: no atomics, no workspace.
+ * NEMAR_EINVAL, nothing launched: a required pointer NULL (d, loss, active, workspace; d, gscale, gd) or not 4-byte aligned (all the
+ * alignment asked for); a non-positive N, H or W; N > 65535; H*W >= 2^31; H > 16 * 65535; gd equal to d;
+ * ws_bytes < nemar_fold_penalty_workspace(). */
+size_t nemar_fold_penalty_workspace(int N, int H, int W);
+int nemar_fold_penalty_fwd(const float* d, float margin, float factor, float* loss, int accumulate, unsigned* active, void* workspace,
+                           size_t ws_bytes, int N, int H, int W, void* stream);
+int nemar_fold_penalty_bwd(const float* d, float margin, const float* gscale, float factor, float* gd, int accumulate, int N, int H,
+                           int W, void* stream);
 
 /* ---- K1/K2/K4/K8: convolution family on fp32 MFMA (exact fp32) ---------------------------------------------
  * nn.Conv2d / nn.ConvTranspose2d with the ReflectionPad2d and torch.cat feeding them folded in —

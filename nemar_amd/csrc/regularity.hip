@@ -20,12 +20,11 @@
 #include <math.h>
 
 #include "common.h"
-#include "resampled_grid.h"
+#include "jacobian_tile.h"
 
 namespace {
 
 constexpr int JAC_WORDS = 8;      // interior (u32), folds (u32), min, max, sum det, sum log det, sum (log det)^2 (f32), one unused
-constexpr int JT_W = RT_W + 1, JT_H = RT_H + 1;      // the tile with its halo column and row
 
 struct JacAcc {
     unsigned interior, folds;
@@ -123,7 +122,7 @@ __global__ __launch_bounds__(RT_THREADS) void jacobian_kernel(const float* __res
             const float* qx = pos + r * JT_W + c;
             const float* qy = qx + JT_H * JT_W;
             const float ix = qx[0], iy = qy[0];
-            det = (qx[1] - ix) * (qy[JT_W] - iy) - (qx[JT_W] - ix) * (qy[1] - iy);
+            det = jac_det(ix, iy, qx[1], qy[1], qx[JT_W], qy[JT_W]);      // (jacobian_tile.h: shared with fold.hip)
             acc.interior += 1u;
             acc.mn = fminf(acc.mn, det);
             acc.mx = fmaxf(acc.mx, det);

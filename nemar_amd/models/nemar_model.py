@@ -12,6 +12,7 @@ executes:
     also the data-parallel all-reduce buckets (nemar_amd.distributed): one bucket after backward_D, two after
     backward_T_and_R.
 """
+import argparse
 import itertools
 import os
 
@@ -82,6 +83,13 @@ class NEMARModel(BaseModel):
             parser.add_argument('--lambda_recon', type=float, default=100.0,
                                 help='Weight for the L1 reconstruction loss.')
             parser.add_argument('--lambda_smooth', type=float, default=0.0, help='Regularization term used by the STN')
+            # (MI355X build) train against folds: a hinge on the Jacobian determinant of the UNet STN's prediction (ops.fold_penalty).
+            # Both default to 0.0 (_fold_options); a command line that does not carry them parses to the options it always parsed to
+            parser.add_argument('--lambda_fold', type=float, default=argparse.SUPPRESS,
+                                help='unet STN only: weight of the fold penalty, mean max(0, fold_margin - Jacobian determinant); '
+                                     'default 0.0: switched off')
+            parser.add_argument('--fold_margin', type=float, default=argparse.SUPPRESS,
+                                help='determinant below which the fold penalty acts (default 0.0: folds only; the identity has determinant ~1)')
             parser.add_argument('--enable_tbvis', action='store_true',
                                 help='Enable tensorboard visualizer (default : False)')
             parser.add_argument('--multi_resolution', type=int, default=1,
@@ -98,6 +106,12 @@ class NEMARModel(BaseModel):
     def __init__(self, opt):
         BaseModel.__init__(self, opt)
         self.train_stn = True
+        # the fold penalty is a term of the training step only, and only a dense field has a per-pixel determinant to train against
+        self._lambda_fold, self._fold_margin = float(getattr(opt, 'lambda_fold', 0.0)), float(getattr(opt, 'fold_margin', 0.0))
+        self._fold_on = bool(self.isTrain and self._lambda_fold != 0.0)
+        if self._fold_on and opt.stn_type != 'unet':
+            raise ValueError('--lambda_fold %g needs --stn_type unet: the %s STN has no fold term (theta\'s determinant is one number per '
+                             'sample, not a field to regularise)' % (self._lambda_fold, opt.stn_type))
         self.setup_visualizers()
         self.tb_visualizer = None
         # T's two applications and D's 3 + 2 applications per step run as single batches: the same graph with half the launches.  (With
@@ -121,12 +135,15 @@ class NEMARModel(BaseModel):
                 self.tb_visualizer = TrainingMonitor(self, opt)
             self._one = torch.ones((), dtype=torch.float32, device=self.device)
             self._lam_smooth = torch.full((), float(opt.lambda_smooth), dtype=torch.float32, device=self.device)
+            if self._fold_on:
+                self._lam_fold = torch.full((), self._lambda_fold, dtype=torch.float32, device=self.device)
 
     loss_L1_TR = _loss_property('L1_TR')
     loss_GAN_TR = _loss_property('GAN_TR')
     loss_L1_RT = _loss_property('L1_RT')
     loss_GAN_RT = _loss_property('GAN_RT')
     loss_smoothness = _loss_property('smoothness')
+    loss_fold = _loss_property('fold')
     loss_D_fake_TR = _loss_property('D_fake_TR')
     loss_D_fake_RT = _loss_property('D_fake_RT')
     loss_D = _loss_property('D')
@@ -134,6 +151,8 @@ class NEMARModel(BaseModel):
     def setup_visualizers(self):
         # <loss>_TR: registration-first branch T(R(a)); <loss>_RT: translation-first branch R(T(a))
         self.loss_names = ['L1_TR', 'GAN_TR', 'L1_RT', 'GAN_RT', 'smoothness', 'D_fake_TR', 'D_fake_RT', 'D']
+        if self._fold_on:
+            self.loss_names.insert(self.loss_names.index('smoothness') + 1, 'fold')
         self.visual_names = ['real_A', 'real_B', 'fake_TR_B', 'fake_RT_B', 'registered_real_A', 'fake_B']
         self.model_names = ['T', 'R'] + (['D'] if self.isTrain else [])
 
@@ -332,7 +351,14 @@ class NEMARModel(BaseModel):
         if not self._batched:
             # the reference's own order (models/nemar_model.py:161-176)
             self.fake_B = self.netT(self.real_A)
-            warped, reg_term = self.netR(self.real_A, self.real_B, apply_on=[self.real_A, self.fake_B])
+            if self._fold_on:
+                # netR.forward() piece by piece, with one more handle of the field for the fold term
+                (f_warp,), f_reg, f_fold = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 1, fold=True)
+                warped = self.netR.warp(f_warp, [self.real_A, self.fake_B])
+                reg_term = self.netR.regularization(f_reg, warped[0])
+                self.stn_fold_term = self.netR.fold_term(f_fold, self._fold_margin)
+            else:
+                warped, reg_term = self.netR(self.real_A, self.real_B, apply_on=[self.real_A, self.fake_B])
             self.stn_reg_term = reg_term
             self.registered_real_A = warped[0]
             self.fake_TR_B = self.netT(self.registered_real_A)     # registration first, then translation
@@ -345,7 +371,10 @@ class NEMARModel(BaseModel):
             n = self.real_A.size(0)
             # (the field has three consumers — two warps and the regulariser —, the batch of T two sources and two slices: the library's own
             # nodes for fan-out, concatenation and slicing, ops.fork / cat_batch / split_batch, instead of autograd's ATen kernels)
-            (f_a, f_b), f_reg = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 2)
+            if self._fold_on:
+                (f_a, f_b), f_reg, f_fold = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 2, fold=True)
+            else:
+                (f_a, f_b), f_reg = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 2)
             self.registered_real_A = self.netR.warp(f_a, [self.real_A])[0]
             # (only the second half is differentiated: the stem's data gradient runs on it alone)
             with ops.norm_segments(2):
@@ -353,6 +382,8 @@ class NEMARModel(BaseModel):
             self.fake_B, self.fake_TR_B = ops.split_batch(both, 2)
             self.fake_RT_B = self.netR.warp(f_b, [self.fake_B])[0]
             self.stn_reg_term = self.netR.regularization(f_reg, self.registered_real_A)
+            if self._fold_on:
+                self.stn_fold_term = self.netR.fold_term(f_fold, self._fold_margin)
         self._resized = {}
         if self.tb_visualizer is not None:
             # the reference runs netR a second time here (get_grid, :172-173); the field of the pass above is the same tensor
@@ -445,9 +476,14 @@ class NEMARModel(BaseModel):
         if opt.lambda_smooth != 0.0:
             roots.append(self.stn_reg_term)         # d(lambda * reg) = lambda * d(reg): the weight is the seed
             grads.append(self._lam_smooth)
+        total = [(r, 1.0) for r in roots[:len(roots) - (1 if opt.lambda_smooth != 0.0 else 0)]] + [(self.stn_reg_term, float(opt.lambda_smooth))]
+        if self._fold_on:
+            self.loss_fold = _LazyLoss([(self.stn_fold_term, self._lambda_fold)])
+            roots.append(self.stn_fold_term)        # one more root, seeded with its weight like the smoothness term
+            grads.append(self._lam_fold)
+            total.append((self.stn_fold_term, self._lambda_fold))
         torch.autograd.backward(roots, grads)
-        return _LazyLoss([(r, 1.0) for r in roots[:len(roots) - (1 if opt.lambda_smooth != 0.0 else 0)]] +
-                         [(self.stn_reg_term, float(opt.lambda_smooth))])
+        return _LazyLoss(total)
 
     # ---- the step as a captured hipGraph (launch-bound small configurations: BASELINE config 1) ---------------------------------
     def enable_step_graph(self, warmup=3):

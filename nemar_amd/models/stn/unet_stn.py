@@ -181,15 +181,28 @@ class UnetSTN(nn.Module):
         """what last_prediction() returns from now on: a composite made outside the forward pass (NEMARModel.cascade)"""
         self.last_offsets = offsets.detach()
 
-    def fork_field(self, field, n_warps):
+    def fork_field(self, field, n_warps, fold=False):
         """-> ([one field per warp() call], the field for regularization()): handles of the same tensors (ops.fork), so that the
-        consumers' gradients are added by the library's kernel instead of autograd's accumulation."""
+        consumers' gradients are added by the library's kernel instead of autograd's accumulation.  With fold=True a third element:
+        one more handle of the field the warp reads, for fold_term()."""
         d, d_up = field
+        extra = 1 if fold else 0
         if d_up is d:
-            hs = ops.fork(d, n_warps + 1)
-            return [(h, h) for h in hs[:n_warps]], (hs[n_warps], hs[n_warps])
-        ups = ops.fork(d_up, n_warps)
-        return [(d, u) for u in ups], (d, d_up)
+            hs = ops.fork(d, n_warps + 1 + extra)
+            out = [(h, h) for h in hs[:n_warps]], (hs[n_warps], hs[n_warps])
+            return (*out, (hs[n_warps + 1], hs[n_warps + 1])) if fold else out
+        ups = ops.fork(d_up, n_warps + extra)
+        out = [(d, u) for u in ups[:n_warps]], (d, d_up)
+        return (*out, (d, ups[n_warps])) if fold else out
+
+    def fold_term(self, field, margin=0.0):
+        """mean over the interior pixels of max(0, margin - det) on the field the warp reads (ops.fold_penalty: the Jacobian
+        determinant regularity() measures at the network's size).  The per-sample count of pixels with det <= margin stays on the
+        device as `last_fold_active` (util/visualizer.FoldMeter)."""
+        term, active = ops.fold_penalty(field[1], margin, 1.0, return_active=True)
+        self.last_fold_active = active
+        self.last_fold_interior = (field[1].size(2) - 1) * (field[1].size(3) - 1)      # per sample: what the counts are a share of
+        return term
 
     def regularization(self, field, warped_first):
         return self._calculate_regularization_term(field[0], warped_first)

@@ -1980,6 +1980,43 @@ def smoothness(d, img=None, alpha=0.0, factor=1.0):
     return _Smoothness.apply(d, img, float(alpha), float(factor))
 
 
+class _FoldPenalty(Function):
+    @staticmethod
+    def forward(ctx, d, margin, factor):
+        d = _c(d)
+        N, _, H, W = d.shape
+        loss = torch.empty((1,), dtype=torch.float32, device=d.device)
+        active = torch.empty((N,), dtype=torch.int32, device=d.device)
+        wsb = Q.fold_penalty_workspace(N, H, W)
+        ws = _workspace(wsb, d.device)
+        L.fold_penalty_fwd(_p(d), margin, factor, _p(loss), 0, _p(active), _p(ws), wsb, N, H, W, _stream())
+        ctx.save_for_backward(d)
+        ctx.cfg = (margin, factor)
+        ctx.mark_non_differentiable(active)
+        return loss.reshape(()), active
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_active):
+        d, = ctx.saved_tensors
+        margin, factor = ctx.cfg
+        N, _, H, W = d.shape
+        gd = torch.empty_like(d)
+        L.fold_penalty_bwd(_p(d), margin, _p(_c(g)), factor, _p(gd), 0, N, H, W, _stream())
+        return gd, None, None
+
+
+def fold_penalty(d, margin=0.0, factor=1.0, return_active=False):
+    """factor * mean over the interior pixels of max(0, margin - det), det the forward-difference Jacobian determinant of the
+    transformation the UNet offsets d [N,2,H,W] describe at their own size (nemar_fold_penalty_fwd / _bwd: the determinant
+    jacobian_stats measures there, bit for bit) — a 0-dim device tensor with a gradient towards d.  With return_active also the int32 [N]
+    count of interior pixels with det <= margin (margin 0: jacobian_stats' folds), no gradient.  No sync."""
+    if d.dim() != 4 or d.shape[1] != 2:
+        raise ValueError("fold_penalty: offsets %s, expected [N,2,H,W]" % (tuple(d.shape),))
+    loss, active = _FoldPenalty.apply(d, float(margin), float(factor))
+    return (loss, active) if return_active else loss
+
+
 class _L1(Function):
     @staticmethod
     def forward(ctx, a, b, weight):

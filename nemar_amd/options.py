@@ -72,6 +72,8 @@ class BaseOptions:
         lines = ['----------------- Options ---------------']
         for k, v in sorted(vars(opt).items()):
             default = self.parser.get_default(k)
+            if default is argparse.SUPPRESS:        # an option that exists only when the command line carries it (--lambda_fold)
+                default = 'not set'
             comment = '\t[default: %s]' % str(default) if v != default else ''
             lines.append('{:>25}: {:<30}{}'.format(str(k), str(v), comment))
         lines.append('----------------- End -------------------')

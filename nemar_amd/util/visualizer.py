@@ -132,6 +132,28 @@ class RegistrationMeter:
         return out
 
 
+class FoldMeter:
+    """Share of the interior pixels on which the fold penalty acts (--lambda_fold): update() adds the step's per-sample counts
+    (ops.fold_penalty's `active`) into a device accumulator, no sync; read() transfers one integer, returns sum active / sum M of
+    everything since the last read (None if nothing was added) and resets."""
+
+    def __init__(self, device):
+        self.acc = torch.zeros((), dtype=torch.int64, device=device)
+        self.pixels = 0
+
+    def update(self, active, interior_per_sample):
+        self.acc.add_(active.sum())
+        self.pixels += active.numel() * int(interior_per_sample)
+
+    def read(self):
+        if self.pixels == 0:
+            return None
+        frac = int(self.acc) / self.pixels                       # the only device->host transfer
+        self.acc.zero_()
+        self.pixels = 0
+        return frac
+
+
 class TrainingMonitor:
     """What train.py drives every iteration (reference TensorboardVisualizer.iteration_step, tb_visualizer.py:68-85)."""
 
@@ -144,6 +166,7 @@ class TrainingMonitor:
         self.report_registration = not getattr(opt, 'tbvis_disable_report_registration', False)
         self.meter = OffsetMeter(model.device)
         self.reg_meter = RegistrationMeter(model.device)
+        self.fold_meter = FoldMeter(model.device) if getattr(model, '_fold_on', False) else None
         self.iteration_cnt = 0
         self.save_count = 0
 
@@ -156,6 +179,9 @@ class TrainingMonitor:
             pred = self.model.netR.last_prediction()             # the prediction of the step's own forward pass: R is not run again
             if pred is not None:
                 self.reg_meter.update(pred[0], pred[1], gt)
+        active = getattr(self.model.netR, 'last_fold_active', None) if self.fold_meter is not None else None
+        if active is not None:
+            self.fold_meter.update(active, self.model.netR.last_fold_interior)
         if self.rate <= 0:
             return
         if self.iteration_cnt == 0:
@@ -197,10 +223,14 @@ class TrainingMonitor:
         self.save_count += 1
 
     def write_registration(self):
-        """'registration/<name>' of everything metered since the last report (nothing without a ground-truth field)"""
+        """'registration/<name>' of everything metered since the last report (nothing without a ground-truth field), and with the
+        fold penalty on 'fold/active_frac'"""
         summary = self.reg_meter.read() if self.report_registration else None
         for name, v in (summary or {}).items():
             self.log.add_scalar('registration/{}'.format(name), v, self.save_count)
+        frac = self.fold_meter.read() if self.fold_meter is not None else None
+        if frac is not None:
+            self.log.add_scalar('fold/active_frac', frac, self.save_count)
 
     def end(self):
         if self.log.writer is not None:
