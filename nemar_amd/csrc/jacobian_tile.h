@@ -18,9 +18,8 @@ __device__ __forceinline__ float jac_det(float ix, float iy, float rx, float ry,
 // p(h, w) of a UNet offset field fN [2,H,W] taken at its own size: the position in pixels that grid_coord<GRID_UNET> + sample_position
 // give the pixel — the call jacobian_kernel<GRID_UNET, false> makes
 __device__ __forceinline__ void unet_position(const float* __restrict__ fN, size_t plane, int h, int w, int H, int W, float& px, float& py) {
-    const FieldPatch none{0, 0, false};
     float gx, gy;
-    resampled_coord<GRID_UNET, false>(nullptr, none, fN, 0, plane, h, w, H, W, H, W, 1.f, 1.f, nullptr, gx, gy);
+    pred_view<GRID_UNET, false>(fN, 0, H, W, H, W, 1.f, 1.f).coord_unstaged(h, w, gx, gy);
     sample_position(gx, gy, W, H, px, py);
 }
 

@@ -16,12 +16,12 @@
 // tools/microbench_register.py times the two side by side and profiles/register_fullres.txt holds the result, 16-byte stores take 27 % to
 // 37 % longer, as in warp.hip's forward kernel (profiles/r4_gs_fwd_vec.txt).  No pointer needs more than 4-byte alignment.
 //
-// Arithmetic is shared, not restated: grid and position from warp_grid.h, the resize taps and their sum from resize_taps.h, the tile's
-// field patch and the texels a pixel reads from resampled_grid.h (shared with score.hip, which counts what this kernel would write), the
-// four-corner blend in the expression order of warp.hip's grid_sample_fwd_kernel.  With -ffp-contract=off the bilinear result equals
-// the composed path's bit for bit (tests/register_cases.py).
+// Arithmetic is shared, not restated: grid and position from warp_grid.h, the resize taps and their sum from resize_taps.h, the
+// prediction's view, the tile's field patch and the texels a pixel reads from resampled_grid.h, the four-corner blend in the
+// expression order of warp.hip's grid_sample_fwd_kernel.  With -ffp-contract=off the bilinear result equals the composed path's bit
+// for bit (tests/register_cases.py).
 #include "common.h"
-#include "resampled_grid.h"
+#include "pred_launch.h"
 
 namespace {
 
@@ -33,21 +33,13 @@ __global__ __launch_bounds__(RT_THREADS) void warp_resampled_kernel(const float*
     __shared__ float patch[RESAMPLE ? 2 * RT_PH * RT_PW : 1];
     const int n = blockIdx.z, tid = threadIdx.x;
     const int x0 = blockIdx.x * RT_W, y0 = blockIdx.y * RT_H;
-    float th[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (MODE == GRID_AFFINE) {
-        affine_theta(pred, n, th);
-    }
-    const size_t splane = (size_t)Hs * Ws, oplane = (size_t)Ho * Wo;
-    const int fplane = RESAMPLE ? hf * wf : 0;
+    const auto pv = pred_view<MODE, RESAMPLE>(pred, n, hf, wf, Ho, Wo, sh, sw);
+    const size_t splane = (size_t)Hs * Ws, oplane = pv.oplane;
     const float* inN = in + (size_t)n * C * splane;
     float* outN = out + (size_t)n * C * oplane;
-    const float* fN = MODE == GRID_UNET ? pred + (size_t)n * 2 * (RESAMPLE ? (size_t)fplane : oplane) : nullptr;
 
-    FieldPatch fp{0, 0, false};
-    if (RESAMPLE) {
-        fp = stage_field(patch, fN, fplane, x0, y0, hf, wf, Ho, Wo, sh, sw, tid);
-        __syncthreads();
-    }
+    const FieldPatch fp = pv.stage(patch, x0, y0, tid);
+    if (RESAMPLE) __syncthreads();
 
     constexpr int LPR = RT_W / VEC, ROWS = RT_THREADS / LPR, RUNS = RT_H / ROWS;      // lanes per tile row, rows per pass, passes
 #pragma unroll
@@ -59,7 +51,7 @@ __global__ __launch_bounds__(RT_THREADS) void warp_resampled_kernel(const float*
         for (int v = 0; v < VEC; ++v) {
             const int w = w0 + v;
             float gx, gy;
-            resampled_coord<MODE, RESAMPLE>(patch, fp, fN, fplane, oplane, h, w, hf, wf, Ho, Wo, sh, sw, th, gx, gy);
+            pv.coord(patch, fp, h, w, gx, gy);
             t[v] = taps_at<SAMPLE>(gx, gy, Ws, Hs);
         }
         float* q = outN + (size_t)h * Wo + w0;
@@ -86,24 +78,13 @@ NEMAR_SWITCH(int, g_register_vec4, 0);
 namespace {
 
 template <int MODE, int SAMPLE, bool RESAMPLE>
-void launch_route(const float* in, const float* pred, float* out, int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, hipStream_t st) {
+void launch(const float* in, const float* pred, float* out, int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, float sh, float sw,
+            hipStream_t st) {
     const dim3 grid(nemar_cdiv(Wo, RT_W), nemar_cdiv(Ho, RT_H), N), block(RT_THREADS);
-    const float sh = (float)hf / (float)Ho, sw = (float)wf / (float)Wo;           // nemar_bilinear_fwd's scales
     NEMAR_AB_ONLY(if (g_register_vec4 && (Wo & 3) == 0 && (((uintptr_t)out) & 15) == 0)
         hipLaunchKernelGGL((warp_resampled_kernel<MODE, SAMPLE, 4, RESAMPLE>), grid, block, 0, st, in, pred, out, C, Hs, Ws, hf, wf, Ho, Wo, sh, sw);
     else)
         hipLaunchKernelGGL((warp_resampled_kernel<MODE, SAMPLE, 1, RESAMPLE>), grid, block, 0, st, in, pred, out, C, Hs, Ws, hf, wf, Ho, Wo, sh, sw);
-}
-
-template <int MODE, int SAMPLE>
-void launch(const float* in, const float* pred, float* out, int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, hipStream_t st) {
-    if constexpr (MODE == GRID_UNET) {
-        if (hf != Ho || wf != Wo) {
-            launch_route<MODE, SAMPLE, true>(in, pred, out, N, C, Hs, Ws, hf, wf, Ho, Wo, st);
-            return;
-        }
-    }
-    launch_route<MODE, SAMPLE, false>(in, pred, out, N, C, Hs, Ws, hf, wf, Ho, Wo, st);
 }
 
 }  // namespace
@@ -114,23 +95,18 @@ NEMAR_API int nemar_warp_resampled_fwd(const float* in, const float* pred, int g
     NEMAR_REQUIRE(in && pred && out, "warp_resampled_fwd: null pointer");
     NEMAR_REQUIRE(((((uintptr_t)in) | ((uintptr_t)pred) | ((uintptr_t)out)) & 3) == 0,
                   "warp_resampled_fwd: in, pred and out must be 4-byte aligned");
-    NEMAR_REQUIRE(grid_mode == GRID_UNET || grid_mode == GRID_AFFINE,
-                  "warp_resampled_fwd: grid_mode %d (NEMAR_GRID_UNET or NEMAR_GRID_AFFINE: an explicit grid has no other resolution)", grid_mode);
     NEMAR_REQUIRE(sample_mode == SAMPLE_BILINEAR || sample_mode == SAMPLE_NEAREST, "warp_resampled_fwd: unknown sample_mode %d", sample_mode);
     NEMAR_REQUIRE(N > 0 && C > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "warp_resampled_fwd: bad shape N=%d C=%d source %dx%d output %dx%d", N,
                   C, Hs, Ws, Ho, Wo);
-    NEMAR_REQUIRE(grid_mode != GRID_UNET || (hf >= 1 && wf >= 1), "warp_resampled_fwd: offset field %d x %d", hf, wf);
-    NEMAR_REQUIRE((long long)Hs * Ws < (1ll << 31) && (long long)Ho * Wo < (1ll << 31) && N <= 65535 && nemar_cdiv(Ho, RT_H) <= 65535 &&
-                      (grid_mode != GRID_UNET || (long long)hf * wf < (1ll << 30)),
-                  "warp_resampled_fwd: plane too large");
+    NEMAR_REQUIRE((long long)Hs * Ws < (1ll << 31), "warp_resampled_fwd: source plane too large");
+    NEMAR_REQUIRE_OK(pred_ok("warp_resampled_fwd", "", grid_mode, hf, wf) && tile_grid_ok("warp_resampled_fwd", N, Ho, Wo));
     hipStream_t st = (hipStream_t)stream;
-    if (grid_mode == GRID_UNET) {
-        if (sample_mode == SAMPLE_NEAREST) launch<GRID_UNET, SAMPLE_NEAREST>(in, pred, out, N, C, Hs, Ws, hf, wf, Ho, Wo, st);
-        else launch<GRID_UNET, SAMPLE_BILINEAR>(in, pred, out, N, C, Hs, Ws, hf, wf, Ho, Wo, st);
-    } else {
-        if (sample_mode == SAMPLE_NEAREST) launch<GRID_AFFINE, SAMPLE_NEAREST>(in, pred, out, N, C, Hs, Ws, 1, 1, Ho, Wo, st);
-        else launch<GRID_AFFINE, SAMPLE_BILINEAR>(in, pred, out, N, C, Hs, Ws, 1, 1, Ho, Wo, st);
-    }
+    dispatch_pred(grid_mode, hf, wf, Ho, Wo, [&](auto mode, auto resample, int hf, int wf, float sh, float sw) {
+        constexpr int MODE = decltype(mode)::value;
+        constexpr bool RESAMPLE = decltype(resample)::value;
+        if (sample_mode == SAMPLE_NEAREST) launch<MODE, SAMPLE_NEAREST, RESAMPLE>(in, pred, out, N, C, Hs, Ws, hf, wf, Ho, Wo, sh, sw, st);
+        else launch<MODE, SAMPLE_BILINEAR, RESAMPLE>(in, pred, out, N, C, Hs, Ws, hf, wf, Ho, Wo, sh, sw, st);
+    });
     NEMAR_CHECK_LAUNCH("warp_resampled_fwd");
     return NEMAR_OK;
 }

@@ -1,8 +1,10 @@
 // Where nemar_warp_resampled_fwd samples, for every kernel that must sample THERE: register.hip (the warp itself), score.hip
-// (nemar_label_overlap, which counts the labels that warp would write without writing them) and compose.hip (nemar_compose_pred, which
-// reads one prediction where another samples).  The 64 x 16 output tile, the coarse-field
-// patch a tile stages in LDS, the pixel's grid coordinate from it, and the texel(s) that coordinate reads — one statement of the
-// arithmetic on top of warp_grid.h and resize_taps.h, so that the two cannot drift apart.
+// (nemar_label_overlap counts the labels that warp would write; nemar_map_points evaluates the grid between the pixels), compose.hip
+// (nemar_compose_pred reads one prediction where another samples), regularity.hip (nemar_jacobian_stats differences the positions),
+// similarity.hip (nemar_joint_histogram bins the values that warp would write) and, through jacobian_tile.h, fold.hip.  The 64 x 16
+// output tile, a prediction as one sample of one launch sees it (PredView: the coarse-field patch a tile stages in LDS and the pixel's
+// grid coordinate from it) and the texel(s) that coordinate reads — one statement of the arithmetic on top of warp_grid.h and
+// resize_taps.h, so that the kernels cannot drift apart.  The host side of a launch over these tiles is in pred_launch.h.
 #pragma once
 #include "common.h"
 #include "resize_taps.h"
@@ -93,39 +95,68 @@ struct FieldPatch {
     int px0, py0;      // the patch's first texel in the field
     bool staged;       // the taps fit the LDS patch (the same in every lane of the workgroup); otherwise they are read from global memory
 };
-// fills `patch` (2 * RT_PH * RT_PW floats of LDS) for the tile at (y0, x0) from the sample's field fN; the caller's __syncthreads() follows
-__device__ __forceinline__ FieldPatch stage_field(float* patch, const float* __restrict__ fN, int fplane, int x0, int y0, int hf, int wf,
-                                                  int Ho, int Wo, float sh, float sw, int tid) {
-    const Tap1D ta = tap1d(x0, wf, sw), tb = tap1d(min(x0 + RT_W, Wo) - 1, wf, sw);
-    const Tap1D tc = tap1d(y0, hf, sh), td = tap1d(min(y0 + RT_H, Ho) - 1, hf, sh);
-    const int pw = tb.i1 - ta.i0 + 1, ph = td.i1 - tc.i0 + 1;
-    FieldPatch fp{ta.i0, tc.i0, pw <= RT_PW && ph <= RT_PH};
-    if (fp.staged) {
-        for (int e = tid; e < 2 * ph * RT_PW; e += RT_THREADS) {
-            const int cr = e / RT_PW, rx = e - cr * RT_PW;      // cr: channel-major row of the patch
-            const int c = cr >= ph ? 1 : 0, ry = cr - c * ph;
-            if (rx < pw) patch[(c * RT_PH + ry) * RT_PW + rx] = fN[(size_t)c * fplane + (size_t)(fp.py0 + ry) * wf + fp.px0 + rx];
-        }
-    }
-    return fp;
-}
-// the normalised grid coordinate of output pixel (h, w): the field value (UNET: interpolated from the patch or the global field when
-// RESAMPLE, read at the pixel otherwise) added to the identity, or theta applied (AFFINE)
+
+// One prediction as one sample of one launch reads it: everything that is fixed for the launch and the sample.  Built inside the kernel
+// from its scalar arguments (pred_view) and indexed with constants only, so that theta and the sizes stay in scalar registers.
+// RESAMPLE: the UNet field has another size (hf, wf) than the output (Ho, Wo) and is interpolated; otherwise it is read at the pixel.
 template <int MODE, bool RESAMPLE>
-__device__ __forceinline__ void resampled_coord(const float* patch, const FieldPatch& fp, const float* __restrict__ fN, int fplane, size_t oplane,
-                                                int h, int w, int hf, int wf, int Ho, int Wo, float sh, float sw, const float* th,
-                                                float& gx, float& gy) {
-    RegSrc src{0.f, 0.f};                          // the pixel's two grid_src values
-    if (MODE == GRID_UNET) {
-        if (RESAMPLE) {
-            const Tap1D ty = tap1d(h, hf, sh), tx = tap1d(w, wf, sw);
-            src = fp.staged ? field_at(patch, RT_PW, RT_PH * RT_PW, fp.py0, fp.px0, ty, tx) : field_at(fN, wf, fplane, 0, 0, ty, tx);
-        } else {
-            const size_t o = (size_t)h * Wo + w;
-            src = RegSrc{fN[o], fN[oplane + o]};
+struct PredView {
+    float th[6];             // AFFINE: theta of the sample
+    const float* fN;         // UNET: the sample's field [2,hf,wf] (RESAMPLE) or [2,Ho,Wo]
+    int fplane;              // hf * wf when RESAMPLE
+    size_t oplane;           // Ho * Wo
+    int hf, wf, Ho, Wo;
+    float sh, sw;            // nemar_bilinear_fwd's scales hf / Ho, wf / Wo
+
+    // fills `patch` (2 * RT_PH * RT_PW floats of LDS) for the tile at (y0, x0); the caller's __syncthreads() follows.  Nothing to stage
+    // without RESAMPLE
+    __device__ __forceinline__ FieldPatch stage(float* patch, int x0, int y0, int tid) const {
+        if (!RESAMPLE) return FieldPatch{0, 0, false};
+        const Tap1D ta = tap1d(x0, wf, sw), tb = tap1d(min(x0 + RT_W, Wo) - 1, wf, sw);
+        const Tap1D tc = tap1d(y0, hf, sh), td = tap1d(min(y0 + RT_H, Ho) - 1, hf, sh);
+        const int pw = tb.i1 - ta.i0 + 1, ph = td.i1 - tc.i0 + 1;
+        const FieldPatch fp{ta.i0, tc.i0, pw <= RT_PW && ph <= RT_PH};
+        if (fp.staged) {
+            for (int e = tid; e < 2 * ph * RT_PW; e += RT_THREADS) {
+                const int cr = e / RT_PW, rx = e - cr * RT_PW;      // cr: channel-major row of the patch
+                const int c = cr >= ph ? 1 : 0, ry = cr - c * ph;
+                if (rx < pw) patch[(c * RT_PH + ry) * RT_PW + rx] = fN[(size_t)c * fplane + (size_t)(fp.py0 + ry) * wf + fp.px0 + rx];
+            }
         }
+        return fp;
     }
-    grid_coord<MODE>(src, h, w, Ho, Wo, th, gx, gy);
+    // the normalised grid coordinate of output pixel (h, w): the field value (UNET: interpolated from the patch or the global field when
+    // RESAMPLE, read at the pixel otherwise) added to the identity, or theta applied (AFFINE)
+    __device__ __forceinline__ void coord(const float* patch, const FieldPatch& fp, int h, int w, float& gx, float& gy) const {
+        RegSrc src{0.f, 0.f};                          // the pixel's two grid_src values
+        if (MODE == GRID_UNET) {
+            if (RESAMPLE) {
+                const Tap1D ty = tap1d(h, hf, sh), tx = tap1d(w, wf, sw);
+                src = fp.staged ? field_at(patch, RT_PW, RT_PH * RT_PW, fp.py0, fp.px0, ty, tx) : field_at(fN, wf, fplane, 0, 0, ty, tx);
+            } else {
+                const size_t o = (size_t)h * Wo + w;
+                src = RegSrc{fN[o], fN[oplane + o]};
+            }
+        }
+        grid_coord<MODE>(src, h, w, Ho, Wo, th, gx, gy);
+    }
+    // the same coordinate where no staged patch covers the pixel: always the global field (jacobian_tile.h; regularity.hip's halo takes
+    // this path per lane, through coord with the patch switched off)
+    __device__ __forceinline__ void coord_unstaged(int h, int w, float& gx, float& gy) const {
+        coord(nullptr, FieldPatch{0, 0, false}, h, w, gx, gy);
+    }
+};
+
+// the view of sample n of `pred` (UNET: the field [N,2,hf,wf]; AFFINE: dtheta [N,6], hf = wf = 1)
+template <int MODE, bool RESAMPLE>
+__device__ __forceinline__ PredView<MODE, RESAMPLE> pred_view(const float* __restrict__ pred, int n, int hf, int wf, int Ho, int Wo, float sh,
+                                                              float sw) {
+    PredView<MODE, RESAMPLE> v{{0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, nullptr, RESAMPLE ? hf * wf : 0, (size_t)Ho * Wo, hf, wf, Ho, Wo, sh, sw};
+    if (MODE == GRID_AFFINE) {
+        affine_theta(pred, n, v.th);
+    }
+    if (MODE == GRID_UNET) v.fN = pred + (size_t)n * 2 * (RESAMPLE ? (size_t)v.fplane : v.oplane);
+    return v;
 }
 
 }  // namespace

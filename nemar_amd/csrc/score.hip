@@ -18,7 +18,7 @@
 // none inside a segment, a few across a boundary — add for themselves.  tools/microbench_score.py times this against per-lane adds
 // (nemar_tune(45, 1), measurement build) on blocky, single-class and per-pixel-random maps: tools/profiles/label_overlap.txt.
 #include "common.h"
-#include "resampled_grid.h"
+#include "pred_launch.h"
 #include "wave_count.h"
 
 namespace {
@@ -47,15 +47,9 @@ __global__ __launch_bounds__(RT_THREADS) void label_overlap_kernel(const float* 
     unsigned* hist = lds.hist;
     float* patch = lds.patch;
     const int n = blockIdx.y, tid = threadIdx.x;
-    float th[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (MODE == GRID_AFFINE) {
-        affine_theta(pred, n, th);
-    }
-    const size_t splane = (size_t)Hs * Ws, oplane = (size_t)Ho * Wo;
-    const int fplane = RESAMPLE ? hf * wf : 0;
-    const float* lmN = lm + (size_t)n * splane;
-    const float* lfN = lf + (size_t)n * oplane;
-    const float* fN = MODE == GRID_UNET ? pred + (size_t)n * 2 * (RESAMPLE ? (size_t)fplane : oplane) : nullptr;
+    const auto pv = pred_view<MODE, RESAMPLE>(pred, n, hf, wf, Ho, Wo, sh, sw);
+    const float* lmN = lm + (size_t)n * Hs * Ws;
+    const float* lfN = lf + (size_t)n * pv.oplane;
 
     for (int e = tid; e < 3 * K; e += RT_THREADS) hist[e] = 0u;
     __syncthreads();
@@ -64,12 +58,9 @@ __global__ __launch_bounds__(RT_THREADS) void label_overlap_kernel(const float* 
     for (int t = blockIdx.x; t < tiles; t += gridDim.x) {         // (the same trip count in every lane of the workgroup)
         const int tyi = t / tiles_x;
         const int x0 = (t - tyi * tiles_x) * RT_W, y0 = tyi * RT_H;
-        FieldPatch fp{0, 0, false};
-        if (RESAMPLE) {
-            __syncthreads();                                      // the previous tile's readers are done with the patch
-            fp = stage_field(patch, fN, fplane, x0, y0, hf, wf, Ho, Wo, sh, sw, tid);
-            __syncthreads();
-        }
+        if (RESAMPLE) __syncthreads();                            // the previous tile's readers are done with the patch
+        const FieldPatch fp = pv.stage(patch, x0, y0, tid);
+        if (RESAMPLE) __syncthreads();
 #pragma unroll
         for (int i = 0; i < RUNS; ++i) {
             const int h = y0 + tid / RT_W + ROWS * i, w = x0 + tid % RT_W;
@@ -77,7 +68,7 @@ __global__ __launch_bounds__(RT_THREADS) void label_overlap_kernel(const float* 
             int km = -1, kf = -1;
             if (inside) {
                 float gx, gy;
-                resampled_coord<MODE, RESAMPLE>(patch, fp, fN, fplane, oplane, h, w, hf, wf, Ho, Wo, sh, sw, th, gx, gy);
+                pv.coord(patch, fp, h, w, gx, gy);
                 const Taps tp = taps_at<SAMPLE_NEAREST>(gx, gy, Ws, Hs);
                 km = class_of(sample_at<SAMPLE_NEAREST>(lmN, tp), K);
                 kf = class_of(lfN[(size_t)h * Wo + w], K);
@@ -130,15 +121,10 @@ namespace {
 
 template <int MODE, bool RESAMPLE>
 void launch_overlap(const float* lm, const float* lf, const float* pred, unsigned* counts, int N, int K, int Hs, int Ws, int hf, int wf, int Ho,
-                    int Wo, hipStream_t st) {
+                    int Wo, float sh, float sw, hipStream_t st) {
     const int tiles_x = nemar_cdiv(Wo, RT_W), tiles = tiles_x * nemar_cdiv(Ho, RT_H);
-    // every workgroup clears and flushes its own 3K counters and walks an equal share of the tiles, so the grid is what the chip holds AT
-    // ONCE and no more: 256 CUs x the workgroups of a CU (LDS: 8 with the small histogram, 6 with the large; a grid one workgroup per CU
-    // larger runs a second, nearly empty round and takes almost twice as long)
-    const int resident = 256 * (K <= 256 ? 8 : 6);
-    const int per_sample = tiles < resident / N ? tiles : (resident / N > 0 ? resident / N : 1);
-    const dim3 grid(per_sample, N), block(RT_THREADS);
-    const float sh = (float)hf / (float)Ho, sw = (float)wf / (float)Wo;           // nemar_bilinear_fwd's scales
+    // every workgroup clears and flushes its own 3K counters (LDS: 8 workgroups per CU with the small histogram, 6 with the large)
+    const dim3 grid(resident_groups(N, K <= 256 ? 8 : 6, tiles), N), block(RT_THREADS);
     if (K <= 256)
         hipLaunchKernelGGL((label_overlap_kernel<MODE, RESAMPLE, 256>), grid, block, 0, st, lm, lf, pred, counts, K, Hs, Ws, hf, wf, Ho, Wo, sh, sw, tiles_x,
                            tiles, (int)g_overlap_per_lane);
@@ -155,22 +141,16 @@ NEMAR_API int nemar_label_overlap(const float* labels_moving, const float* label
     NEMAR_REQUIRE(labels_moving && labels_fixed && pred && counts, "label_overlap: null pointer");
     NEMAR_REQUIRE(((((uintptr_t)labels_moving) | ((uintptr_t)labels_fixed) | ((uintptr_t)pred) | ((uintptr_t)counts)) & 3) == 0,
                   "label_overlap: labels_moving, labels_fixed, pred and counts must be 4-byte aligned");
-    NEMAR_REQUIRE(grid_mode == GRID_UNET || grid_mode == GRID_AFFINE,
-                  "label_overlap: grid_mode %d (NEMAR_GRID_UNET or NEMAR_GRID_AFFINE: an explicit grid has no other resolution)", grid_mode);
     NEMAR_REQUIRE(N > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "label_overlap: bad shape N=%d source %dx%d output %dx%d", N, Hs, Ws, Ho, Wo);
     NEMAR_REQUIRE(K >= 1 && K <= MAX_CLASSES, "label_overlap: %d classes (1 .. %d)", K, MAX_CLASSES);
-    NEMAR_REQUIRE(grid_mode != GRID_UNET || (hf >= 1 && wf >= 1), "label_overlap: offset field %d x %d", hf, wf);
-    NEMAR_REQUIRE((long long)Hs * Ws < (1ll << 31) && (long long)Ho * Wo < (1ll << 31) && N <= 65535 &&
-                      (grid_mode != GRID_UNET || (long long)hf * wf < (1ll << 30)),
-                  "label_overlap: plane too large");
+    NEMAR_REQUIRE((long long)Hs * Ws < (1ll << 31), "label_overlap: source plane too large");
+    NEMAR_REQUIRE_OK(pred_ok("label_overlap", "", grid_mode, hf, wf) && tile_grid_ok("label_overlap", N, Ho, Wo));
     hipStream_t st = (hipStream_t)stream;
     NEMAR_HIP_CALL(hipMemsetAsync(counts, 0, (size_t)N * K * 3 * sizeof(unsigned), st));
-    if (grid_mode == GRID_UNET) {
-        if (hf != Ho || wf != Wo) launch_overlap<GRID_UNET, true>(labels_moving, labels_fixed, pred, counts, N, K, Hs, Ws, hf, wf, Ho, Wo, st);
-        else launch_overlap<GRID_UNET, false>(labels_moving, labels_fixed, pred, counts, N, K, Hs, Ws, hf, wf, Ho, Wo, st);
-    } else {
-        launch_overlap<GRID_AFFINE, false>(labels_moving, labels_fixed, pred, counts, N, K, Hs, Ws, 1, 1, Ho, Wo, st);
-    }
+    dispatch_pred(grid_mode, hf, wf, Ho, Wo, [&](auto mode, auto resample, int hf, int wf, float sh, float sw) {
+        launch_overlap<decltype(mode)::value, decltype(resample)::value>(labels_moving, labels_fixed, pred, counts, N, K, Hs, Ws, hf, wf, Ho, Wo,
+                                                                         sh, sw, st);
+    });
     NEMAR_CHECK_LAUNCH("label_overlap");
     return NEMAR_OK;
 }
@@ -180,11 +160,10 @@ NEMAR_API int nemar_map_points(const float* pts, const float* pred, int grid_mod
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(pts && pred && out, "map_points: null pointer");
     NEMAR_REQUIRE(((((uintptr_t)pts) | ((uintptr_t)pred) | ((uintptr_t)out)) & 3) == 0, "map_points: pts, pred and out must be 4-byte aligned");
-    NEMAR_REQUIRE(grid_mode == GRID_UNET || grid_mode == GRID_AFFINE,
-                  "map_points: grid_mode %d (NEMAR_GRID_UNET or NEMAR_GRID_AFFINE)", grid_mode);
     NEMAR_REQUIRE(N > 0 && N <= 65535 && P > 0 && Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0, "map_points: bad shape N=%d P=%d source %dx%d output %dx%d",
                   N, P, Hs, Ws, Ho, Wo);
-    NEMAR_REQUIRE(grid_mode != GRID_UNET || (hf >= 1 && wf >= 1 && (long long)hf * wf < (1ll << 30)), "map_points: offset field %d x %d", hf, wf);
+    // (no tile grid: a point needs no output plane, and (Ho, Wo) may be any size)
+    NEMAR_REQUIRE_OK(pred_ok("map_points", "", grid_mode, hf, wf));
     if (grid_mode != GRID_UNET) hf = wf = 1;
     hipLaunchKernelGGL(map_points_kernel, dim3(nemar_cdiv(P, 64), N), dim3(64), 0, (hipStream_t)stream, pts, pred, grid_mode, out, P, Hs, Ws, hf, wf,
                        Ho, Wo, (float)hf / (float)Ho, (float)wf / (float)Wo);
