@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 610 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 611 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -117,6 +117,40 @@ int nemar_fold_penalty_fwd(const float* d, float margin, float factor, float* lo
                            size_t ws_bytes, int N, int H, int W, void* stream);
 int nemar_fold_penalty_bwd(const float* d, float margin, const float* gscale, float factor, float* gd, int accumulate, int N, int H,
                            int W, void* stream);
+
+/* Scaling and squaring (csrc/integrate.hip; not in the reference, whose UNet STN warps with the network's output as it is): the network's
+ * output as a stationary velocity field v, the warp reads exp(v).  One squaring step on a displacement field u [N,2,H,W], planar, in the
+ * units of NEMAR_GRID_UNET offsets.  Channel 0 times W/2 and channel 1 times H/2 are pixels.  s is a scale:
+ *   a      = s * u                                   (one fp32 product; s == 1 leaves the bits alone)
+ *   p(h,w) = ( clamp(w + a0(h,w) * W/2, 0, W-1),  clamp(h + a1(h,w) * H/2, 0, H-1) )
+ *   out(h,w) = a(h,w) + bilinear(a, p(h,w))          both channels, align_corners=True texel centres (true identity: a zero field
+ *                                                    samples its own texel), border texel outside the image
+ * The zoom of linspace(-1,1) under align_corners=False (what NEMAR_GRID_UNET adds to the offsets) stays where it is, in the final warp
+ * only: the integration itself uses a true identity, K squarings would otherwise apply that zoom 2^K times.  bilinear: x0 = floor(p.x),
+ * x1 = min(x0 + 1, W-1), t = p.x - x0 (the same in y), a00 (1-tx)(1-ty) + a01 tx (1-ty) + a10 (1-tx) ty + a11 tx ty.  Positions are
+ * clamped in float before the integer conversion (NaN -> 0): no input value indexes outside the plane.
+ * Gradient with respect to u given gout: three parts, each times s.
+ *   The direct term is gout(x).
+ *   The image path is w_k(x') * gout(x') scattered into the four corners of every p(x').
+ *   The position path at the texel itself is sum_ch gout_ch(x) * d bilinear_ch / d p_c * (W/2 or H/2) * s.  It is zero along an axis
+ *   whose raw position was clamped (raw < 0 or raw > size-1).
+ * bwd: gu = (accumulate ? gu : 0) + s * ((direct + position) + image), the bracket rounded to fp32 before it is added.  The image path
+ * goes through 64-bit fixed-point integer atomics into the zeroed leading bytes of the workspace — each w * gout rounded to a multiple of
+ * 2^(e - FIX), 2^(e-1) <= max |gout| of the call < 2^e (found on the device; e clamped at -80), FIX = min(40, 62 - ceil(log2(H W))): no
+ * overflow even if every pixel of a plane lands on one texel — no fp32 atomics: bitwise repeatable, whatever the field.  No host sync.
+ * Workspace: nemar_svf_step_bwd_workspace() bytes, 8-byte aligned, whose first nemar_svf_step_bwd_zeroed_bytes() are zero on entry and
+ * left zero on return (the contract of nemar_grid_sample_bwd_workspace); the rest is scratch.  Non-finite u or gout: NEMAR_OK, nothing
+ * outside the buffers is touched, the zeroed bytes come back zero; the values have no meaning.
+ * Chain: integrate(v, K, sign) is u_0 = v, then K steps.  The first step carries s = sign / 2^K and the others s = 1.  K = 0 is the
+ * identity (sign * v).  sign = -1 gives exp(-v), the inverse of exp(v) in this true-identity convention (it does not undo the warp's
+ * zoom).
+ * NEMAR_EINVAL, nothing launched: a required pointer NULL or misaligned; a non-positive N, H or W; N > 65535; H*W >= 2^31;
+ * H > 16 * 65535; out == u; gu == u; gu == gout; ws_bytes < nemar_svf_step_bwd_workspace(). */
+int nemar_svf_step_fwd(const float* u, float scale, float* out, int N, int H, int W, void* stream);
+size_t nemar_svf_step_bwd_workspace(int N, int H, int W);
+size_t nemar_svf_step_bwd_zeroed_bytes(int N, int H, int W);
+int nemar_svf_step_bwd(const float* u, float scale, const float* gout, float* gu, int accumulate, void* workspace, size_t ws_bytes,
+                       int N, int H, int W, void* stream);
 
 /* ---- K1/K2/K4/K8: convolution family on fp32 MFMA (exact fp32) ---------------------------------------------
  * nn.Conv2d / nn.ConvTranspose2d with the ReflectionPad2d and torch.cat feeding them folded in —

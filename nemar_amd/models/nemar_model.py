@@ -265,7 +265,8 @@ class NEMARModel(BaseModel):
         return told
 
     def register(self, full_A, full_B=None, labels_A=None, translate=True, labels_B=None, landmarks_A=None, landmarks_B=None,
-                 num_classes=None, regularity=False, jacobian_map=False, similarity=False, bins=32, intensity_range=(-1., 1.)):
+                 num_classes=None, regularity=False, jacobian_map=False, similarity=False, bins=32, intensity_range=(-1., 1.),
+                 inverse=False):
         """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the
         network's resolution) predicted: the sampling grid is in normalised coordinates, so the prediction holds at every size, and the
         warp kernel resizes a dense field on the fly (ops.warp_resampled).  full_A [N,C,H,W] is modality A of the same N pairs at any
@@ -292,10 +293,20 @@ class NEMARModel(BaseModel):
         netR.similarity of full_A against full_B at full_B's size — the joint histogram int64 [N,bins,bins] of the two channel means
         over intensity_range (the value range of the images handed in) and the moments float32 [N,6] — under the identity and under
         the prediction (ops.similarity_summary: mutual information, NCC, MSE, MAE).  No annotation is needed.  Two more launch pairs;
-        nothing else in the dict changes."""
+        nothing else in the dict changes.
+        With inverse=True (needs --stn_integrate K > 0 and full_B, which is read) 'registered_B', full_B warped onto A at its own size by
+        the inverse prediction, and 'inverse_offsets' [N,2,h,w], that prediction: exp(-v) of the velocity the network predicted
+        (netR.inverse_prediction: K more squaring steps).  It inverts the integrated map in its true-identity convention and does not
+        undo the slight zoom of the warp's grid."""
         pred = self.netR.last_prediction()
         if pred is None:
             raise RuntimeError('register: no forward pass yet')
+        if inverse:
+            if getattr(self.netR, 'integrate', 0) <= 0:
+                raise ValueError('register: inverse=True needs a UNet STN built with --stn_integrate K > 0 (a velocity field to integrate '
+                                 'backwards); this one predicts a displacement')
+            if full_B is None:
+                raise ValueError('register: inverse=True needs full_B, the images to warp onto A')
         with torch.no_grad():
             full_A = full_A.to(self.device, dtype=torch.float32).contiguous()
             if full_A.size(0) != pred[0].size(0):
@@ -337,6 +348,13 @@ class NEMARModel(BaseModel):
                 zeros = torch.zeros((pred[0].size(0), 6), dtype=torch.float32, device=self.device)
                 out['similarity'] = {'before': ops.joint_histogram(zeros, ops.GRID_AFFINE, full_A, full_B, bins, intensity_range, intensity_range),
                                      'after': self.netR.similarity(pred, full_A, full_B, bins, intensity_range, intensity_range)}
+            if inverse:
+                inv = self.netR.inverse_prediction()
+                full_B = full_B.to(self.device, dtype=torch.float32).contiguous()
+                if full_B.size(0) != inv[0].size(0):
+                    raise ValueError('register: %d fixed images for a prediction of %d pairs' % (full_B.size(0), inv[0].size(0)))
+                out['registered_B'] = self.netR.apply(inv, [full_B])[0]
+                out['inverse_offsets'] = inv[0]
         return out
 
     def _netT_runs_at(self, h, w):

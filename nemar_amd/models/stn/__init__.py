@@ -22,6 +22,11 @@ _FLAGS = (
 )
 
 
+def _integrate(opt):
+    """--stn_integrate (0 where the option set does not carry it: a Namespace built before the flag existed)"""
+    return int(getattr(opt, 'stn_integrate', 0))
+
+
 def _flag(opt, name):
     """opt.<name>, or the flag's default where the command line did not carry it (the train-only flags on a test command line: they
     configure the regulariser and the initialisation, which inference does not use)"""
@@ -32,14 +37,22 @@ def _flag(opt, name):
 _BUILDERS = {
     'affine': lambda a, b, h, w, opt: AffineSTN(a, b, h, w, opt.stn_cfg, opt.init_type),
     'unet': lambda a, b, h, w, opt: UnetSTN(a, b, h, w, opt.stn_cfg, opt.init_type, _flag(opt, 'stn_bilateral_alpha'),
-                                            not _flag(opt, 'stn_no_identity_init'), _flag(opt, 'stn_multires_reg')),
+                                            not _flag(opt, 'stn_no_identity_init'), _flag(opt, 'stn_multires_reg'),
+                                            integrate=_integrate(opt)),
 }
 
 
 def modify_commandline_options(parser, is_train=True):
+    import argparse
     for flag, kw, train_only in _FLAGS:
         if is_train or not train_only:
             parser.add_argument(flag, **kw)
+    # (MI355X build) diffeomorphic UNet STN: the network's output as a stationary velocity field, the warp reads exp(v) integrated by K
+    # scaling-and-squaring steps (ops.integrate_velocity).  For train AND test: a checkpoint trained with it must be registered with it.
+    # SUPPRESS: an option set without the flag is the set of before it existed (read with getattr(opt, 'stn_integrate', 0))
+    parser.add_argument('--stn_integrate', type=int, default=argparse.SUPPRESS,
+                        help='unet only: integrate the predicted field as a stationary velocity by this many scaling-and-squaring steps '
+                             '(0 = off: the field is the displacement, as the reference has it; 6 is a usual choice)')
     return parser
 
 
@@ -50,6 +63,11 @@ def define_stn(opt, stn_type='affine'):
     make = _BUILDERS.get(stn_type)
     if make is None:
         return None
+    k = _integrate(opt)
+    if k < 0 or k > 30:
+        raise ValueError('--stn_integrate %d: the number of squaring steps, 0 .. 30' % k)
+    if k > 0 and stn_type != 'unet':
+        raise ValueError('--stn_integrate %d needs --stn_type unet: the %s STN predicts no field to integrate' % (k, stn_type))
     a_to_b = opt.direction == 'AtoB'
     net = make(opt.input_nc if a_to_b else opt.output_nc, opt.output_nc if a_to_b else opt.input_nc, opt.img_height, opt.img_width, opt)
     if len(opt.gpu_ids) > 0:

@@ -97,22 +97,53 @@ class UnetSTN(nn.Module):
     """Predicts the deformation and applies it (reference :105-201)."""
 
     def __init__(self, in_channels_a, in_channels_b, height, width, cfg, init_func, stn_bilateral_alpha,
-                 init_to_identity, multi_resolution_regularization):
+                 init_to_identity, multi_resolution_regularization, integrate=0):
+        """integrate = K > 0 (--stn_integrate; not in the reference): the network's output is a stationary VELOCITY field and the warp
+        reads exp(v), K scaling-and-squaring steps at the network's size (ops.integrate_velocity) — a composition of 2^K near-identity
+        maps, free of folds up to discretisation and the clamp at the border.  0: the output is the displacement itself."""
         super().__init__()
         self.oh, self.ow = height, width
         self.in_channels_a, self.in_channels_b = in_channels_a, in_channels_b
         self.offset_map = ResUnet(in_channels_a, in_channels_b, cfg, init_func, init_to_identity)
         self.alpha = stn_bilateral_alpha
         self.multi_resolution_regularization = multi_resolution_regularization
+        self.integrate = int(integrate)
+
+    def _resized(self, d):
+        """the reference's low-resolution branch (:139,165): `and`, as there"""
+        if d.size(2) != self.oh and d.size(3) != self.ow:
+            return ops.resize_bilinear(d, self.oh, self.ow)
+        return d
 
     def _deformation(self, img_a, img_b):
         d = self.offset_map(img_a, img_b)
-        if d.size(2) != self.oh and d.size(3) != self.ow:       # `and`, as in the reference (:139,165)
-            d_up = ops.resize_bilinear(d, self.oh, self.ow)
-        else:
-            d_up = d
+        if self.integrate > 0:
+            # field[0] stays the velocity (the smoothness regulariser acts on it, as the diffeomorphic VoxelMorph line does); everything
+            # that reads field[1] — the warp, the fold term, last_prediction() — sees the integrated field.  Two handles of the velocity,
+            # one per consumer: their gradients are added by the library's kernel
+            v_int, v_reg = ops.fork(d, 2)
+            self.last_velocity = d.detach()        # no copy
+            d_up = self._resized(ops.integrate_velocity(v_int, self.integrate))
+            self.last_offsets = d_up.detach()
+            return v_reg, d_up
+        d_up = self._resized(d)
         self.last_offsets = d_up.detach()          # for the offset statistics (util/visualizer.OffsetMeter); no copy
         return d, d_up
+
+    def inverse_prediction(self):
+        """(offsets, grid mode) of the INVERSE of the last prediction: exp(-v), one more integration of the last velocity — usable
+        wherever a prediction is (apply, overlap, map_points, regularity, similarity, compose).  It inverts exp(v) in the integration's
+        true-identity convention: it does not undo the slight zoom the warp's linspace grid adds, so
+        apply(inverse) after apply(forward) is two of those zooms away from the identity.  None before the first pass.  No autograd."""
+        if self.integrate <= 0:
+            raise RuntimeError('inverse_prediction: this UnetSTN predicts a displacement, not a velocity (integrate = 0: build it with '
+                               '--stn_integrate K > 0)')
+        v = getattr(self, 'last_velocity', None)
+        if v is None:
+            return None
+        import torch
+        with torch.no_grad():
+            return self._resized(ops.integrate_velocity(v, self.integrate, -1.0)), ops.GRID_UNET
 
     def last_prediction(self):
         """(what the last forward pass handed to the warp kernel, its grid mode) — None before the first pass"""
@@ -180,6 +211,7 @@ class UnetSTN(nn.Module):
     def set_last_prediction(self, offsets):
         """what last_prediction() returns from now on: a composite made outside the forward pass (NEMARModel.cascade)"""
         self.last_offsets = offsets.detach()
+        self.last_velocity = None                  # a composite is the exponential of no single velocity: it has no inverse_prediction()
 
     def fork_field(self, field, n_warps, fold=False):
         """-> ([one field per warp() call], the field for regularization()): handles of the same tensors (ops.fork), so that the

@@ -2017,6 +2017,63 @@ def fold_penalty(d, margin=0.0, factor=1.0, return_active=False):
     return (loss, active) if return_active else loss
 
 
+def _svf_scales(steps, sign):
+    """the scale each squaring step carries: sign / 2^K on the first, 1 on the others"""
+    return [float(sign) / float(1 << steps)] + [1.0] * (steps - 1)
+
+
+class _IntegrateVelocity(Function):
+    @staticmethod
+    def forward(ctx, v, steps, sign):
+        v = _c(v)
+        N, _, H, W = v.shape
+        st = _stream()
+        inputs, u = [], v
+        for s in _svf_scales(steps, sign):
+            out = torch.empty_like(u)
+            with _span('svf_step_fwd'):
+                L.svf_step_fwd(_p(u), s, _p(out), N, H, W, st)
+            inputs.append(u)
+            u = out
+        ctx.save_for_backward(*inputs)              # the K step inputs: the velocity and the K - 1 intermediate fields
+        ctx.cfg = (steps, sign)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        inputs = ctx.saved_tensors
+        steps, sign = ctx.cfg
+        g = _c(g)
+        N, _, H, W = g.shape
+        st = _stream()
+        wsb = Q.svf_step_bwd_workspace(N, H, W)
+        ws = _zeroed_workspace(wsb, (g.device, 'svf', N, H, W))      # leading part: all-zero in, all-zero out; rest: scratch
+        for u, s in zip(reversed(inputs), reversed(_svf_scales(steps, sign))):
+            gu = torch.empty_like(u)
+            with _span('svf_step_bwd'):
+                L.svf_step_bwd(_p(u), s, _p(g), _p(gu), 0, _p(ws), wsb, N, H, W, st)
+            g = gu
+        return g, None, None
+
+
+def integrate_velocity(v, steps, sign=1.0):
+    """exp(sign * v) of a stationary velocity field v [N,2,H,W] (NEMAR_GRID_UNET offset units) by scaling and squaring: `steps` = K calls of
+    nemar_svf_step_fwd, the first with the scale sign / 2^K (include/nemar_hip.h).  The displacement of a composition of 2^K near-identity
+    maps: no folds by construction, up to discretisation and the clamp at the border.  sign = -1 integrates -v: the inverse.  The
+    integration's identity is a true one; the slight zoom of the warp's linspace grid is not part of it.  One autograd node whose backward
+    walks the saved step inputs in reverse (nemar_svf_step_bwd: bitwise repeatable, no fp32 atomics).  No sync, no ATen kernel.
+    steps = 0 returns v (times sign) without a launch."""
+    if v.dim() != 4 or v.shape[1] != 2:
+        raise ValueError("integrate_velocity: velocity %s, expected [N,2,H,W]" % (tuple(v.shape),))
+    steps = int(steps)
+    if steps < 0 or steps > 30:
+        raise ValueError("integrate_velocity: steps %d (0 .. 30)" % steps)
+    if steps == 0:
+        return v if float(sign) == 1.0 else v * float(sign)
+    return _IntegrateVelocity.apply(v, steps, float(sign))
+
+
 class _L1(Function):
     @staticmethod
     def forward(ctx, a, b, weight):

@@ -144,5 +144,8 @@ class TestOptions(BaseOptions):
         # A.npy / B.npy alone: NEMARModel.register(similarity=True)); --bins: the joint histogram's bins per side (2 .. 64)
         a('--similarity', action='store_true')
         a('--bins', type=int, default=32)
+        # python -m nemar_amd.register: registered_B.npy and inverse_offsets.npy, B warped onto A by the inverse prediction
+        # (NEMARModel.register(inverse=True); needs --stn_integrate K > 0).  SUPPRESS: absent from an option set that does not ask for it
+        a('--inverse', action='store_true', default=argparse.SUPPRESS)
         self.isTrain = False
         return parser

@@ -35,6 +35,11 @@ Written under --results_dir/--name/:
                               form from a --bins x --bins joint histogram of the channel means over [0, 1]; NCC, MSE and MAE; with
                               --passes K > 1 also `per_pass`, K such summaries of the network-size pair after each pass.  Needs no
                               annotation: A.npy and B.npy are enough (csrc/similarity.hip)
+    registered_B.npy          only with --inverse (needs --stn_integrate K > 0, the flag the model was trained with, and --passes 1):
+                              modality B warped onto A by the inverse prediction, in B.npy's own size, layout and dtype
+    inverse_offsets.npy       only with --inverse: that prediction [M,2,h,w], exp(-v) of the velocity field the network predicted
+                              (csrc/integrate.hip).  It inverts the integrated map in its true-identity convention; the slight zoom
+                              of the warp's grid is not undone
 and one summary line on stdout: pairs, sizes, the scores (with --regularity: folds in per cent and SDlogJ; with --similarity:
 MI before -> after), seconds."""
 import json
@@ -152,6 +157,13 @@ def main(argv=None):
     per_pass = [[] for _ in range(opt.passes)] if want_reg and opt.passes > 1 else []
     sim = {'before': [], 'after': []}
     sim_per_pass = [[] for _ in range(opt.passes)] if opt.similarity and opt.passes > 1 else []
+    want_inverse = bool(getattr(opt, 'inverse', False))
+    if want_inverse and (int(getattr(opt, 'stn_integrate', 0)) <= 0 or opt.stn_type != 'unet'):
+        raise SystemExit('--inverse needs --stn_type unet --stn_integrate K > 0: the inverse is exp(-v) of the velocity field such a model predicts')
+    if want_inverse and opt.passes > 1:
+        raise SystemExit('--inverse with --passes %d: a composite of several predictions is the exponential of no single velocity' % opt.passes)
+    raw_B = np.load(os.path.join(opt.dataroot, 'B.npy'), mmap_mode='r') if want_inverse else None
+    reg_B, inv_offsets = [], []
     reg, reg_labels, offsets = [], [], []
     for i0 in range(0, M, opt.batch_size):
         idx = list(range(i0, min(M, i0 + opt.batch_size)))
@@ -169,7 +181,11 @@ def main(argv=None):
         out = model.register(part(pool_A), part(pool_B), part(labels), translate=False,          # (fake_RT_B is not among the files this command writes)
                              labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes,
                              **(dict(regularity=True, jacobian_map=opt.jacobian_map) if want_reg else {}),
-                             **(dict(similarity=True, bins=opt.bins, intensity_range=(0.0, 1.0)) if opt.similarity else {}))
+                             **(dict(similarity=True, bins=opt.bins, intensity_range=(0.0, 1.0)) if opt.similarity else {}),
+                             **(dict(inverse=True) if want_inverse else {}))
+        if want_inverse:
+            reg_B.append(out['registered_B'])
+            inv_offsets.append(out['inverse_offsets'].clone())
         for k in sim:
             if 'similarity' in out:
                 sim[k].append(out['similarity'][k])
@@ -189,6 +205,9 @@ def main(argv=None):
     np.save(os.path.join(out_dir, 'offsets.npy'), torch.cat(offsets).cpu().numpy())
     if labels is not None:
         np.save(os.path.join(out_dir, 'registered_labels_A.npy'), _like_input(torch.cat(reg_labels), raw_labels, False))
+    if want_inverse:
+        np.save(os.path.join(out_dir, 'registered_B.npy'), _like_input(torch.cat(reg_B), raw_B, True))
+        np.save(os.path.join(out_dir, 'inverse_offsets.npy'), torch.cat(inv_offsets).cpu().numpy())
     told = ''
     if scored['overlap'] or scored['tre_px']:
         host = {k: torch.cat(v).cpu().numpy() if v else None for k, v in scored.items()}
