@@ -57,7 +57,11 @@ extern "C" {
  *   45 nemar_label_overlap: every lane adds to the workgroup's LDS histogram for itself (1) / the lanes that share the wave's first key are
  *      added once, by a ballot (0, default; tools/profiles/label_overlap.txt)
  *   46 nemar_joint_histogram: every lane adds to the workgroup's LDS table for itself (1, default) / the lanes that share the wave's first
- *      cell are added once, by a ballot (0: 0 - 3 % slower at 2048^2, tools/profiles/joint_histogram.txt) */
+ *      cell are added once, by a ballot (0: 0 - 3 % slower at 2048^2, tools/profiles/joint_histogram.txt)
+ *   47 nemar_bilinear_fwd / nemar_bilinear_bwd at exactly 2x up, nemar_maxpool2_bwd and the pad-1 reflect fold behind a padded-domain data
+ *      gradient: row-vector kernels (a lane owns 4 or 8 consecutive outputs of a row, 16-byte loads and stores) where W % 4 == 0 and the
+ *      tensors are 16-byte aligned (1, default) / the one-element-per-lane kernels everywhere (0).  The same bits either way
+ *      (profiles/pointwise_rows.txt) */
 int nemar_tune(int key, int value);
 int nemar_tune_ptr(void* timeline_buffer);   /* device buffer for per-stage cycle stamps (tools/timeline_*.py), NULL = off */
 /* grad_input variant for A/B measurements: 0 (default) = gather + fixed point (needs the workspace), 1 = fp32 atomics through an

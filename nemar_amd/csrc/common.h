@@ -51,6 +51,15 @@ extern int g_lds_claim;      // nemar_tune(37, mask)
 constexpr int g_lds_claim = NEMAR_LDS_CLAIM_DEFAULT;
 #endif
 
+// Row-vector forms of the plain data-movement passes (pointwise.hip: 2x resize forward / backward, max-pool backward; conv.hip: reflect
+// fold): nemar_tune(47) in the measurement build, 1 (default, the product) = where shape and alignment allow, 0 = the
+// one-element-per-lane kernels everywhere.  Same bits either way.
+#ifdef NEMAR_AB
+extern int g_pointwise_rows;      // pointwise.hip
+#else
+constexpr int g_pointwise_rows = 1;
+#endif
+
 // include/nemar_hip.h's nemar_conv_extras (the per-call side inputs of nemar_conv2d_*_ex), field for field
 struct nemar_conv_extras {
     void* scratch;
@@ -125,6 +134,15 @@ static inline FastDiv make_fastdiv(unsigned d) {
 }
 __device__ __forceinline__ unsigned fd_div(unsigned n, const FastDiv& f) {
     return (unsigned)(((unsigned long long)n * f.m) >> 40);
+}
+
+// Row-vector kernels: unit u of a [planes][rows][runs] launch (a run = the 4 or 8 consecutive elements of one row that a lane owns).
+// 32-bit divisions, once per run (the callers keep planes * rows * runs below 2^31).
+__device__ __forceinline__ void row_unit(unsigned u, unsigned runs, unsigned rows, int& run, int& row, size_t& plane) {
+    const unsigned t = u / runs, p = t / rows;
+    run = (int)(u - t * runs);
+    row = (int)(t - p * rows);
+    plane = p;
 }
 
 // Direct global -> LDS copies (no VGPR staging): each lane supplies its own global address, the LDS destination is the

@@ -427,8 +427,65 @@ __global__ __launch_bounds__(256) void reflect_fold_kernel(const float* __restri
         gx[idx] = addend ? s + addend[idx] : s;
     }
 }
+// ... for pad == 1 and rows of whole 4-float runs: a lane owns 4 consecutive texels of one row (unit = plane, row, run: row_unit, common.h).
+// The interior is a copy (+ addend) of padded[h + 1][w + 1 ..]: one 16-byte load at a 4-byte aligned address, one 16-byte store.  Only
+// rows 1 and H - 2 have a mirror row (padded rows 0 and H + 1), only texels 1 and W - 2 of a row a mirror column (padded columns 0 and
+// W + 1): the first and the last run of a row load those two words, rows 1 and H - 2 the mirror row's 16 bytes as well — every load of a
+// unit before the first use.  The sums are reflect_fold_kernel's: rows own, upper mirror, lower mirror; within a row own, left, right; the addend last.
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));      // 16-byte load at a 4-byte-aligned address
+template <bool ADD>
+__global__ __launch_bounds__(256) void reflect_fold_rows_kernel(const float* __restrict__ gp, float* __restrict__ gx, int H, int W,
+                                                                unsigned units, const float* __restrict__ addend) {
+    const int Hp = H + 2, Wp = W + 2;
+    const unsigned runs = (unsigned)W >> 2;
+    for (unsigned u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+        int j, h;
+        size_t nc;
+        row_unit(u, runs, H, j, h, nc);
+        const bool up = h == 1, dn = h == H - 2, le = j == 0, ri = j == (int)runs - 1;
+        const float* q = gp + nc * Hp * Wp;
+        const float* r0 = q + (size_t)(h + 1) * Wp;
+        const float* r1 = up ? q : r0;                              // padded row 0 mirrors onto row 1
+        const float* r2 = dn ? q + (size_t)(H + 1) * Wp : r0;       // padded row H + 1 onto row H - 2
+        const int x0 = 4 * j + 1;
+        const size_t o = (nc * H + h) * W + 4 * j;
+        const f32x4u v0 = *reinterpret_cast<const f32x4u*>(r0 + x0);
+        f32x4u v1 = v0, v2 = v0;
+        float l0 = 0.f, l1 = 0.f, l2 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (up) v1 = *reinterpret_cast<const f32x4u*>(r1 + x0);
+        if (dn) v2 = *reinterpret_cast<const f32x4u*>(r2 + x0);
+        if (le) { l0 = r0[0]; l1 = r1[0]; l2 = r2[0]; }
+        if (ri) { e0 = r0[W + 1]; e1 = r1[W + 1]; e2 = r2[W + 1]; }
+        if (ADD) a = *reinterpret_cast<const float4*>(addend + o);
+        // texel 1 of the run is w == 1 in the first run, texel 2 is w == W - 2 in the last
+        float s0 = v0.x, s1 = v0.y, s2 = v0.z, s3 = v0.w;
+        if (le) s1 += l0;
+        if (ri) s2 += e0;
+        if (up) {
+            float t1 = v1.y, t2 = v1.z;
+            if (le) t1 += l1;
+            if (ri) t2 += e1;
+            s0 += v1.x; s1 += t1; s2 += t2; s3 += v1.w;
+        }
+        if (dn) {
+            float t1 = v2.y, t2 = v2.z;
+            if (le) t1 += l2;
+            if (ri) t2 += e2;
+            s0 += v2.x; s1 += t1; s2 += t2; s3 += v2.w;
+        }
+        *reinterpret_cast<float4*>(gx + o) = ADD ? make_float4(s0 + a.x, s1 + a.y, s2 + a.z, s3 + a.w) : make_float4(s0, s1, s2, s3);
+    }
+}
 // the padded domain's gradient folded onto the image (+ addend)
 void fold_padded(const float* padded, float* gx, int H, int W, int pad, long long total, const float* addend, hipStream_t st) {
+    if (g_pointwise_rows && pad == 1 && (W & 3) == 0 && total / 4 < (1ll << 31) &&
+        (((uintptr_t)padded) & 3) == 0 && ((((uintptr_t)gx) | ((uintptr_t)addend)) & 15) == 0) {
+        const dim3 grid(nemar_stream_grid(total / 4, 256)), block(256);
+        if (addend) hipLaunchKernelGGL((reflect_fold_rows_kernel<true>), grid, block, 0, st, padded, gx, H, W, (unsigned)(total / 4), addend);
+        else hipLaunchKernelGGL((reflect_fold_rows_kernel<false>), grid, block, 0, st, padded, gx, H, W, (unsigned)(total / 4), addend);
+        return;
+    }
     hipLaunchKernelGGL(reflect_fold_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, padded, gx, H, W, pad, total, addend);
 }
 
@@ -976,6 +1033,7 @@ NEMAR_API int nemar_tune(int key, int value) {
     if (key == 45) { g_overlap_per_lane = value != 0; return NEMAR_OK; }  // nemar_label_overlap: every lane adds to the LDS histogram itself (1) / wave-aggregated adds (0, default)
     if (key == 46) { g_histogram_per_lane = value != 0; return NEMAR_OK; }  // nemar_joint_histogram: every lane adds to the LDS table itself (1, default) / wave-aggregated adds (0)
     if (key == 44) { g_register_vec4 = value != 0; return NEMAR_OK; }   // nemar_warp_resampled_fwd: 4 pixels per lane + 16-byte stores (1) / one pixel per lane (0, default)
+    if (key == 47) { g_pointwise_rows = value != 0; return NEMAR_OK; }  // row-vector forms of pool backward / 2x resize / reflect fold (1, default) / one element per lane (0)
     if (key == 35) { g_dual_gy = value != 0; return NEMAR_OK; }
     if (key == 34) { nemar_split16_wgrad_tune(value); return NEMAR_OK; }      // wide weight gradient: 1 one gy copy (default), 0 KS shifted copies
     if (key == 30) { g_s16g_fold = value != 0; return NEMAR_OK; }

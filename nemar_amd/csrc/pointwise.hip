@@ -218,6 +218,152 @@ __global__ __launch_bounds__(256) void bilinear_up2_bwd_kernel(const float* __re
     }
 }
 
+// ---- row-vector forms of max-pool backward and the 2x resize (the training step's shapes: W % 4 == 0, 16-byte aligned tensors) ------
+// A lane owns a run of 4 or 8 consecutive outputs of one row (every store 16 bytes); the flat unit index walks [plane][row][run], so
+// consecutive lanes write consecutive memory and a unit costs two 32-bit divisions (row_unit, common.h) instead of two 64-bit ones per
+// element.  Source rows arrive as 16-byte loads plus the one neighbour word on either side, from addresses clamped into the row; every
+// load of a unit is issued before the first use.  Each output is the SAME floating-point expression as in the one-element kernels above
+// (same taps, same order, same border weights): the two forms agree bit for bit, the border ring included.
+
+__device__ __forceinline__ int pool_argmax(float v0, float v1, float v2, float v3) {      // first maximum, row-major (maxpool2_bwd_kernel's comparisons)
+    int am = 0;
+    float m = v0;
+    if (v1 > m) { m = v1; am = 1; }
+    if (v2 > m) { m = v2; am = 2; }
+    if (v3 > m) { m = v3; am = 3; }
+    return am;
+}
+
+// unit = (plane, row pair, 4 columns): two windows, x read once.  The last row of an odd H has no window: addend or 0.
+template <bool ADD>
+__global__ __launch_bounds__(256) void maxpool2_bwd_rows_kernel(const float* __restrict__ x, const float* __restrict__ gy,
+                                                                const float* __restrict__ addend, float* __restrict__ gx, int H,
+                                                                int W, unsigned units) {
+    const int Ho = H >> 1, Wo = W >> 1;
+    const unsigned runs = (unsigned)W >> 2, pairs = ((unsigned)H + 1) >> 1;
+    for (unsigned u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+        int j, rp;
+        size_t nc;
+        row_unit(u, runs, pairs, j, rp, nc);
+        const int h0 = 2 * rp;
+        const bool win = h0 + 1 < H;
+        const size_t o0 = (nc * H + h0) * W + 4 * j, o1 = win ? o0 + W : o0;
+        const float4 a = *reinterpret_cast<const float4*>(x + o0), b = *reinterpret_cast<const float4*>(x + o1);
+        const float2 g = *reinterpret_cast<const float2*>(gy + (nc * Ho + (win ? rp : Ho - 1)) * Wo + 2 * j);
+        float4 s0 = make_float4(0.f, 0.f, 0.f, 0.f), s1 = s0;
+        if (ADD) {
+            s0 = *reinterpret_cast<const float4*>(addend + o0);
+            s1 = *reinterpret_cast<const float4*>(addend + o1);
+        }
+        const int am0 = win ? pool_argmax(a.x, a.y, b.x, b.y) : -1, am1 = win ? pool_argmax(a.z, a.w, b.z, b.w) : -1;
+        const float g00 = am0 == 0 ? g.x : 0.f, g01 = am0 == 1 ? g.x : 0.f, g10 = am0 == 2 ? g.x : 0.f, g11 = am0 == 3 ? g.x : 0.f;
+        const float g02 = am1 == 0 ? g.y : 0.f, g03 = am1 == 1 ? g.y : 0.f, g12 = am1 == 2 ? g.y : 0.f, g13 = am1 == 3 ? g.y : 0.f;
+        *reinterpret_cast<float4*>(gx + o0) =
+            ADD ? make_float4(s0.x + g00, s0.y + g01, s0.z + g02, s0.w + g03) : make_float4(g00, g01, g02, g03);
+        if (win)
+            *reinterpret_cast<float4*>(gx + o1) =
+                ADD ? make_float4(s1.x + g10, s1.y + g11, s1.z + g12, s1.w + g13) : make_float4(g10, g11, g12, g13);
+    }
+}
+
+// exact 2x up, forward.  unit = (plane, output row, 8 output columns 8j .. 8j+7): source columns 4j-1 .. 4j+4 of the two source rows.
+// Output column 2k takes sources (k-1, k), column 2k+1 takes (k, min(k+1, W-1)); column 0 takes (0, 1) with weights (1, 0).  tap1d() still
+// makes every weight; its indices only pick among the registers.
+__global__ __launch_bounds__(256) void bilinear_up2_fwd_rows_kernel(const float* __restrict__ x, float* __restrict__ y, int H, int W,
+                                                                    float sh, float sw, unsigned units) {
+    const int Ho = 2 * H, Wo = 2 * W;
+    const unsigned runs = (unsigned)Wo >> 3;
+    for (unsigned u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+        int j, ho;
+        size_t nc;
+        row_unit(u, runs, Ho, j, ho, nc);
+        const Tap1D th = tap1d(ho, H, sh);
+        const int k0 = 4 * j, wo0 = 8 * j;
+        const float* r0 = x + (nc * H + th.i0) * W + k0;
+        const float* r1 = x + (nc * H + th.i1) * W + k0;
+        const int lo = k0 > 0 ? -1 : 0, hi = k0 + 4 < W ? 4 : 3;
+        const float4 a = *reinterpret_cast<const float4*>(r0), b = *reinterpret_cast<const float4*>(r1);
+        const float al = r0[lo], ar = r0[hi], bl = r1[lo], br = r1[hi];
+        const Tap1D t0 = tap1d(wo0, W, sw), t1 = tap1d(wo0 + 1, W, sw), t2 = tap1d(wo0 + 2, W, sw), t3 = tap1d(wo0 + 3, W, sw),
+                    t4 = tap1d(wo0 + 4, W, sw), t5 = tap1d(wo0 + 5, W, sw), t6 = tap1d(wo0 + 6, W, sw), t7 = tap1d(wo0 + 7, W, sw);
+        const bool first = t0.i0 == k0;      // output column 0: sources (0, 1), not (-1, 0)
+        float4 o0, o1;
+        o0.x = resize_blend(first ? a.x : al, first ? a.y : a.x, first ? b.x : bl, first ? b.y : b.x, t0, th);
+        o0.y = resize_blend(a.x, a.y, b.x, b.y, t1, th);
+        o0.z = resize_blend(a.x, a.y, b.x, b.y, t2, th);
+        o0.w = resize_blend(a.y, a.z, b.y, b.z, t3, th);
+        o1.x = resize_blend(a.y, a.z, b.y, b.z, t4, th);
+        o1.y = resize_blend(a.z, a.w, b.z, b.w, t5, th);
+        o1.z = resize_blend(a.z, a.w, b.z, b.w, t6, th);
+        o1.w = resize_blend(a.w, ar, b.w, br, t7, th);
+        float* q = y + (nc * Ho + ho) * Wo + wo0;
+        *reinterpret_cast<float4*>(q) = o0;
+        *reinterpret_cast<float4*>(q + 4) = o1;
+    }
+}
+
+// exact 2x up, backward.  unit = (plane, row h, 4 columns 4j .. 4j+3): gy columns 8j-1 .. 8j+8 of the rows 2h, 2h+1, 2h+2, 2h-1 — up2_taps'
+// order and weights, rows outside, columns inside; the taps a border lacks are skipped (their loads re-read row 2h / stay inside the row).
+__device__ __forceinline__ float up2_cols(float c0, float c1, float c2, float c3, float wa, float wb, bool next, bool prev) {
+    float r = 0.f;
+    r += wa * c0;
+    r += wb * c1;
+    if (next) r += 0.25f * c2;
+    if (prev) r += 0.25f * c3;
+    return r;
+}
+struct Up2Row { float4 lo, hi; float l, r; };
+__device__ __forceinline__ Up2Row up2_load(const float* q, int lo, int hi) {
+    Up2Row v;
+    v.lo = *reinterpret_cast<const float4*>(q);
+    v.hi = *reinterpret_cast<const float4*>(q + 4);
+    v.l = q[lo];
+    v.r = q[hi];
+    return v;
+}
+__device__ __forceinline__ float4 up2_row4(const Up2Row& v, float wa0, bool prev0, float wb3, bool next3) {
+    float4 r;
+    r.x = up2_cols(v.lo.x, v.lo.y, v.lo.z, v.l, wa0, 0.75f, true, prev0);
+    r.y = up2_cols(v.lo.z, v.lo.w, v.hi.x, v.lo.y, 0.75f, 0.75f, true, true);
+    r.z = up2_cols(v.hi.x, v.hi.y, v.hi.z, v.lo.w, 0.75f, 0.75f, true, true);
+    r.w = up2_cols(v.hi.z, v.hi.w, v.r, v.hi.y, 0.75f, wb3, next3, true);
+    return r;
+}
+__device__ __forceinline__ float up2_rows(float ra, float rb, float rc, float rd, float wa, float wb, bool next, bool prev) {
+    float s = 0.f;
+    s += wa * ra;
+    s += wb * rb;
+    if (next) s += 0.25f * rc;
+    if (prev) s += 0.25f * rd;
+    return s;
+}
+__global__ __launch_bounds__(256) void bilinear_up2_bwd_rows_kernel(const float* __restrict__ gy, float* __restrict__ gx, int H, int W,
+                                                                    unsigned units) {
+    const int Wo = 2 * W, Ho = 2 * H;
+    const unsigned runs = (unsigned)W >> 2;
+    for (unsigned u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+        int j, h;
+        size_t nc;
+        row_unit(u, runs, H, j, h, nc);
+        const int w0 = 4 * j;
+        const bool hn = h + 1 < H, hp = h >= 1, wfirst = w0 == 0, wlast = w0 + 4 == W;
+        const float* p = gy + (nc * Ho + 2 * h) * Wo + 2 * w0;
+        const int lo = wfirst ? 0 : -1, hi = wlast ? 7 : 8;
+        const Up2Row va = up2_load(p, lo, hi), vb = up2_load(p + Wo, lo, hi), vc = up2_load(hn ? p + 2 * Wo : p, lo, hi),
+                     vd = up2_load(hp ? p - Wo : p, lo, hi);
+        const float wa0 = wfirst ? 1.f : 0.75f, wb3 = wlast ? 1.f : 0.75f;
+        const float4 ra = up2_row4(va, wa0, !wfirst, wb3, !wlast), rb = up2_row4(vb, wa0, !wfirst, wb3, !wlast),
+                     rc = up2_row4(vc, wa0, !wfirst, wb3, !wlast), rd = up2_row4(vd, wa0, !wfirst, wb3, !wlast);
+        const float wya = h == 0 ? 1.f : 0.75f, wyb = h == H - 1 ? 1.f : 0.75f;
+        float4 s;
+        s.x = up2_rows(ra.x, rb.x, rc.x, rd.x, wya, wyb, hn, hp);
+        s.y = up2_rows(ra.y, rb.y, rc.y, rd.y, wya, wyb, hn, hp);
+        s.z = up2_rows(ra.z, rb.z, rc.z, rd.z, wya, wyb, hn, hp);
+        s.w = up2_rows(ra.w, rb.w, rc.w, rd.w, wya, wyb, hn, hp);
+        *reinterpret_cast<float4*>(gx + (nc * H + h) * W + w0) = s;
+    }
+}
+
 // ---- dropout: counter-based Philox4x32-10, 4 elements per counter; the mask is regenerated in backward ----------------
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
                                               unsigned* out) {
@@ -300,6 +446,20 @@ __global__ __launch_bounds__(256) void crop_flip_normalize_kernel(const float* _
     }
 }
 
+}  // namespace
+
+// nemar_tune(47, 0) (measurement build): the one-element-per-lane kernels everywhere; 1 (default, and the product): the row-vector forms
+// where rows_ok (conv.hip reads the same switch for reflect_fold_kernel's)
+#ifdef NEMAR_AB
+int g_pointwise_rows = 1;
+#endif
+
+namespace {
+// may a row-vector kernel take the call?  rows that are whole 4-float runs, 16-byte aligned tensors (a null pointer = an absent
+// optional tensor), a unit count the 32-bit unit index holds
+inline bool rows_ok(int W, long long units, const void* a, const void* b, const void* c = nullptr, const void* d = nullptr) {
+    return (W & 3) == 0 && units > 0 && units < (1ll << 31) && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
 }  // namespace
 
 NEMAR_API int nemar_act_bwd(const float* gy, const float* y, float* gx, long long n, int act, float slope, void* stream) {
@@ -416,6 +576,12 @@ NEMAR_API int nemar_maxpool2_bwd(const float* x, const float* gy, const float* a
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(x && gy && gx && planes > 0 && H >= 2 && W >= 2, "maxpool2_bwd: bad arguments");
     const long long total = (long long)planes * H * W;
+    const long long units = (long long)planes * ((H + 1) / 2) * (W / 4);
+    if (g_pointwise_rows && rows_ok(W, units, x, gy, addend, gx)) {
+        const dim3 grid(nemar_stream_grid(units, 256)), block(256);
+        if (addend) hipLaunchKernelGGL((maxpool2_bwd_rows_kernel<true>), grid, block, 0, (hipStream_t)stream, x, gy, addend, gx, H, W, (unsigned)units);
+        else hipLaunchKernelGGL((maxpool2_bwd_rows_kernel<false>), grid, block, 0, (hipStream_t)stream, x, gy, addend, gx, H, W, (unsigned)units);
+    } else
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, gy,
                        addend, gx, H, W, H / 2, W / 2, total);
     NEMAR_CHECK_LAUNCH("maxpool2_bwd");
@@ -426,6 +592,10 @@ NEMAR_API int nemar_bilinear_fwd(const float* x, float* y, int planes, int H, in
     NEMAR_CLEAR_HIP_ERROR();
     NEMAR_REQUIRE(x && y && planes > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0, "bilinear_fwd: bad arguments");
     const long long total = (long long)planes * Ho * Wo;
+    if (g_pointwise_rows && Ho == 2 * H && Wo == 2 * W && rows_ok(W, total / 8, x, y))
+        hipLaunchKernelGGL(bilinear_up2_fwd_rows_kernel, dim3(nemar_stream_grid(total / 8, 256)), dim3(256), 0, (hipStream_t)stream, x, y,
+                           H, W, (float)H / (float)Ho, (float)W / (float)Wo, (unsigned)(total / 8));
+    else
     hipLaunchKernelGGL(bilinear_fwd_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, H,
                        W, Ho, Wo, (float)H / (float)Ho, (float)W / (float)Wo, total);
     NEMAR_CHECK_LAUNCH("bilinear_fwd");
@@ -439,6 +609,10 @@ NEMAR_API int nemar_bilinear_bwd(const float* gy, float* gx, int planes, int H, 
     hipStream_t st = (hipStream_t)stream;
     if (Ho == 2 * H && Wo == 2 * W) {
         const long long total = (long long)planes * H * W;
+        if (g_pointwise_rows && rows_ok(W, total / 4, gy, gx))
+            hipLaunchKernelGGL(bilinear_up2_bwd_rows_kernel, dim3(nemar_stream_grid(total / 4, 256)), dim3(256), 0, st, gy, gx, H, W,
+                               (unsigned)(total / 4));
+        else
         hipLaunchKernelGGL(bilinear_up2_bwd_kernel, dim3(nemar_stream_grid(total, 256)), dim3(256), 0, st, gy, gx, H, W,
                            total);
     } else if (Ho > 0 && Wo > 0 && H % Ho == 0 && W % Wo == 0 && H / Ho >= 2 && W / Wo >= 2) {
