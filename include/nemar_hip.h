@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 611 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 612 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -633,6 +633,40 @@ size_t nemar_joint_histogram_workspace(int N, int Ho, int Wo);
 int nemar_joint_histogram(const float* moving, const float* fixed, const float* pred, int grid_mode, unsigned* counts, float* moments,
                           void* workspace, size_t ws_bytes, int N, int Cm, int Cf, int bins, float lo_m, float hi_m, float lo_f,
                           float hi_f, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* stream);
+
+/* Boundary agreement of a registration (csrc/surface.hip; not in the reference, which has no evaluation code): the distances between the
+ * class boundaries of the warped moving label map and of the fixed label map, from which the Hausdorff distance, its 95th percentile
+ * (HD95) and the average symmetric surface distance (ASSD) follow.  Everything happens on the fixed image's plane Ho x Wo at pixel
+ * spacing 1.  labels_moving, labels_fixed, pred, grid_mode, hf and wf are what nemar_label_overlap takes.
+ *   m(x) = the class (nemar_label_overlap's rule: k iff the value == (float)k for an integer 0 <= k < K, else no class) of the value
+ *          nemar_warp_resampled_fwd(..., NEMAR_SAMPLE_NEAREST) would write at x — the same code computes it; zero padding is class 0;
+ *   f(x) = the class of labels_fixed(x).
+ * A BOUNDARY pixel of class k in a map is a pixel of class k with at least one 4-neighbour that is not of class k; a neighbour outside
+ * the plane is not of class k (S ^ binary_erosion(S), 4-connected, border_value = 0: MedPy's convention), so a class that fills the
+ * plane has the plane's border as its boundary.  A pixel of no class is never a boundary pixel.
+ * Direction 0 (moving -> fixed): for every boundary pixel p of class k in m, d2(p) = min over the boundary pixels q of class k in f of
+ * |p - q|^2, a non-negative integer.  Direction 1 swaps the maps.  The pair (sample, class) is DEFINED when the class has boundary
+ * pixels in both maps; otherwise it has no distances.
+ * With B = max_dist * max_dist:
+ *   counts [N,K,2,3] uint32 (OVERWRITTEN) per sample, class and direction: [0] boundary pixels (counted whether or not the pair is
+ *          defined), [1] far = those with d2 >= B, [2] the largest d2; far and the largest d2 are 0 where the pair is not defined;
+ *   hist   [N,K,2,B] uint32 (OVERWRITTEN): hist[n,k,dir,b] = boundary pixels with d2 == b; all zero where the pair is not defined;
+ *   dist2  [N,2,Ho,Wo] int32 or NULL: plane 0 holds d2 at every boundary pixel of m, plane 1 at every boundary pixel of f; -1 where the
+ *          pixel is no boundary pixel, -2 at a boundary pixel whose pair is not defined.  counts and hist are the same bits without it.
+ * counts and hist are cleared on `stream` by the entry point.  Everything after the warp's coordinate is integer arithmetic, added with
+ * integer atomics (atomicAdd, atomicMax): exact, independent of the order of arrival, bitwise repeatable; no host synchronisation.
+ * The workspace holds the two class maps twice (with and without the boundary flag, 16 bits per pixel) and, for one chunk of classes
+ * at a time, two 16-bit planes of vertical distances per class and sample: the entry point takes min(K, max(1, 128 MiB / (4 N Ho Wo)))
+ * classes per chunk, so nemar_surface_distance_workspace = 8 N Ho Wo + that many * 4 N Ho Wo bytes (0 for a shape the call refuses).
+ * A class without boundary pixels on either side costs no sweep of the plane: the kernels read the counts on the device.
+ * NEMAR_EINVAL, nothing written: labels_moving, labels_fixed, pred, counts, hist or workspace NULL; any given pointer not 4-byte
+ * aligned; K outside 1 .. 1024; max_dist outside 1 .. 128; Ho or Wo above 32768 (so that d2 < 2^31); a non-positive size; N > 65535;
+ * Hs*Ws >= 2^31; a grid_mode other than NEMAR_GRID_UNET / NEMAR_GRID_AFFINE; hf or wf < 1 with NEMAR_GRID_UNET (a field plane >= 2^30);
+ * workspace_bytes < nemar_surface_distance_workspace(). */
+size_t nemar_surface_distance_workspace(int N, int K, int Ho, int Wo);
+int nemar_surface_distance(const float* labels_moving, const float* labels_fixed, const float* pred, int grid_mode, unsigned* counts,
+                           unsigned* hist, int* dist2, void* workspace, size_t workspace_bytes, int N, int K, int max_dist, int Hs, int Ws,
+                           int hf, int wf, int Ho, int Wo, void* stream);
 
 /* ---- K13: losses (already multiplied by their lambda `weight`; optionally accumulated into a device scalar) ------
  * l1:  torch.nn.L1Loss — reference models/nemar_model.py:68,179,195; b == NULL gives mean|a|

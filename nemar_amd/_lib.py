@@ -114,6 +114,8 @@ SIGNATURES = {
     "nemar_jacobian_stats": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "nemar_joint_histogram_workspace": (_sz, [_i, _i, _i]),
     "nemar_joint_histogram": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _i, _i, _i, _i, _i, _i, _vp]),
+    "nemar_surface_distance_workspace": (_sz, [_i, _i, _i, _i]),
+    "nemar_surface_distance": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_dropout": (_i, [_vp, _vp, _ll, _fl, _u64, _u32, _vp]),
     "nemar_dropout_max": (_i, [_vp, _vp, _i, _ll, _fl, _u64, _u32, _vp, _vp]),
     "nemar_loss_workspace": (_sz, []),

@@ -266,7 +266,7 @@ class NEMARModel(BaseModel):
 
     def register(self, full_A, full_B=None, labels_A=None, translate=True, labels_B=None, landmarks_A=None, landmarks_B=None,
                  num_classes=None, regularity=False, jacobian_map=False, similarity=False, bins=32, intensity_range=(-1., 1.),
-                 inverse=False):
+                 inverse=False, surface=False, surface_max_dist=64, surface_map=False):
         """Register images at their native size with the transformation the last forward pass (test() on the set_input batch, at the
         network's resolution) predicted: the sampling grid is in normalised coordinates, so the prediction holds at every size, and the
         warp kernel resizes a dense field on the fly (ops.warp_resampled).  full_A [N,C,H,W] is modality A of the same N pairs at any
@@ -294,6 +294,12 @@ class NEMARModel(BaseModel):
         over intensity_range (the value range of the images handed in) and the moments float32 [N,6] — under the identity and under
         the prediction (ops.similarity_summary: mutual information, NCC, MSE, MAE).  No annotation is needed.  Two more launch pairs;
         nothing else in the dict changes.
+        With surface=True (labels_A, labels_B and num_classes are needed) 'surface' = {'before': (counts, hist), 'after': (counts, hist)}:
+        netR.surface of labels_A against labels_B at labels_B's size — per class and direction the boundary pixels, those farther than
+        surface_max_dist and the largest squared distance, int64 [N,K,2,3], and the histogram of the squared boundary distances, int32
+        [N,K,2,surface_max_dist^2] — under the identity and under the prediction (ops.surface_summary: Hausdorff distance, HD95, ASSD);
+        with surface_map=True also 'surface_dist2' int32 [N,2,H,W], the squared distance at every boundary pixel of the warped map
+        (plane 0) and of labels_B (plane 1) under the prediction.  Nothing else in the dict changes.
         With inverse=True (needs --stn_integrate K > 0 and full_B, which is read) 'registered_B', full_B warped onto A at its own size by
         the inverse prediction, and 'inverse_offsets' [N,2,h,w], that prediction: exp(-v) of the velocity the network predicted
         (netR.inverse_prediction: K more squaring steps).  It inverts the integrated map in its true-identity convention and does not
@@ -301,6 +307,8 @@ class NEMARModel(BaseModel):
         pred = self.netR.last_prediction()
         if pred is None:
             raise RuntimeError('register: no forward pass yet')
+        if surface and (labels_A is None or labels_B is None or num_classes is None):
+            raise ValueError('register: surface=True needs labels_A, labels_B and num_classes, the two label maps and their class count')
         if inverse:
             if getattr(self.netR, 'integrate', 0) <= 0:
                 raise ValueError('register: inverse=True needs a UNet STN built with --stn_integrate K > 0 (a velocity field to integrate '
@@ -348,6 +356,13 @@ class NEMARModel(BaseModel):
                 zeros = torch.zeros((pred[0].size(0), 6), dtype=torch.float32, device=self.device)
                 out['similarity'] = {'before': ops.joint_histogram(zeros, ops.GRID_AFFINE, full_A, full_B, bins, intensity_range, intensity_range),
                                      'after': self.netR.similarity(pred, full_A, full_B, bins, intensity_range, intensity_range)}
+            if surface:
+                zeros = torch.zeros((pred[0].size(0), 6), dtype=torch.float32, device=self.device)
+                before = ops.surface_distance(zeros, ops.GRID_AFFINE, labels_A, labels_B, num_classes, surface_max_dist)
+                after = self.netR.surface(pred, labels_A, labels_B, num_classes, surface_max_dist, bool(surface_map))
+                out['surface'] = {'before': before[:2], 'after': after[:2]}
+                if surface_map:
+                    out['surface_dist2'] = after[2]
             if inverse:
                 inv = self.netR.inverse_prediction()
                 full_B = full_B.to(self.device, dtype=torch.float32).contiguous()

@@ -95,6 +95,13 @@ class AffineSTN(nn.Module):
         apply(..., sample='nearest') gives, never written — against labels_fixed at its size (ops.label_overlap).  No autograd."""
         return ops.label_overlap(prediction_tensor(field), ops.GRID_AFFINE, labels_moving, labels_fixed, num_classes)
 
+    def surface(self, field, labels_moving, labels_fixed, num_classes, max_dist=64, dist_map=False):
+        """Boundary distances of labels_moving warped by the prediction — what apply(..., sample='nearest') gives, never written —
+        against labels_fixed at its size: (counts [N,K,2,3] = boundary pixels, far, largest squared distance per class and direction;
+        hist [N,K,2,max_dist^2] of the squared distances; the distance map [N,2,Ho,Wo] or None) — ops.surface_distance;
+        ops.surface_summary turns counts and hist into the Hausdorff distance, HD95 and ASSD.  No autograd."""
+        return ops.surface_distance(prediction_tensor(field), ops.GRID_AFFINE, labels_moving, labels_fixed, num_classes, max_dist, dist_map)
+
     def map_points(self, field, pts, src_hw, out_hw):
         """Where the prediction samples the src_hw source for points [N,P,2] (x, y) given in pixels of the out_hw fixed image
         (ops.map_points).  No autograd."""

@@ -1755,6 +1755,98 @@ def label_overlap(pred, grid_mode, labels_moving, labels_fixed, num_classes):
     return counts
 
 
+SURFACE_COUNT_COLUMNS = ('boundary', 'far', 'max_d2')
+MAX_SURFACE_DIST = 128
+
+
+def surface_distance(pred, grid_mode, labels_moving, labels_fixed, num_classes, max_dist=64, dist_map=False):
+    """Boundary agreement of a registration (nemar_surface_distance): labels_moving [N,Hs,Ws] (or [N,1,Hs,Ws]) warped by the prediction
+    with nearest sampling — exactly what warp_resampled(..., sample='nearest') returns, but never written — against labels_fixed
+    [N,Ho,Wo] at its size.  A boundary pixel of class k is a pixel of class k with a 4-neighbour (or the plane's edge) that is not;
+    direction 0 measures from the warped map's boundary pixels to the fixed map's boundary of the same class, direction 1 the other way,
+    as squared pixel distances d2 (integers, exact).  Returns (counts int64 [N,K,2,3], columns SURFACE_COUNT_COLUMNS per class and
+    direction: boundary pixels, those with d2 >= max_dist^2, the largest d2; hist int32 [N,K,2,max_dist^2]: boundary pixels per value
+    of d2; dist2 int32 [N,2,Ho,Wo] with dist_map, else None: d2 at the boundary pixels of the warped map (plane 0) and of the fixed map
+    (plane 1), -1 off the boundaries, -2 where the class has no boundary in the other map) as device tensors; a class without boundary
+    pixels in both maps has no distances (far, max_d2 and hist are 0).  surface_summary turns counts and hist into HD, HD95 and ASSD.
+    An identity prediction (GRID_AFFINE, zeros [N,6]) gives the distances before registration.  counts and hist are the same bits with
+    and without the map.  No autograd, no sync."""
+    pred, N, hf, wf = _prediction("surface_distance", pred, grid_mode)
+    lm, lf = _label_planes("surface_distance", labels_moving, N), _label_planes("surface_distance", labels_fixed, N)
+    K, D = int(num_classes), int(max_dist)
+    if not 1 <= D <= MAX_SURFACE_DIST:
+        raise ValueError("surface_distance: max_dist %d (1 .. %d)" % (D, MAX_SURFACE_DIST))
+    Ho, Wo = int(lf.shape[1]), int(lf.shape[2])
+    counts = torch.empty((N, K, 2, 3), dtype=torch.int32, device=lf.device)
+    hist = torch.empty((N, K, 2, D * D), dtype=torch.int32, device=lf.device)
+    dist2 = torch.empty((N, 2, Ho, Wo), dtype=torch.int32, device=lf.device) if dist_map else None
+    wsb = Q.surface_distance_workspace(N, K, Ho, Wo)
+    # (up to 128 MiB of distance planes beside the class maps: the call's own block, back with the caching allocator afterwards, and not
+    # the grow-only workspace the training step keeps)
+    ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=lf.device)
+    L.surface_distance(_p(lm), _p(lf), _p(pred), grid_mode, _p(counts), _p(hist), _p(dist2), _p(ws), wsb, N, K, D, int(lm.shape[1]),
+                       int(lm.shape[2]), hf, wf, Ho, Wo, _stream())
+    return counts.to(torch.int64), hist, dist2             # (uint32 counts below 2^31: the int32 view holds them)
+
+
+def _order_statistic(cum, rank):
+    """the bin that holds the rank-th smallest (0-based) of the values a cumulative histogram counts, or None beyond its last bin"""
+    b = int(np.searchsorted(cum, rank, side='right'))
+    return b if b < len(cum) else None
+
+
+def surface_summary(counts, hist):
+    """What Learn2Reg-style evaluations report next to Dice and SDlogJ, from surface_distance's counts [M,K,2,3] and hist [M,K,2,B] of
+    any number of samples (tensors or arrays; the batches concatenated along the first axis), on the host in float64, in pixels.
+    Per class, over the samples where the class has a boundary in both maps (the pair is defined):
+      hd      sqrt of the larger of the two directions' max_d2: the Hausdorff distance, always exact;
+      asd_mf, asd_fm, assd   the mean distance of each direction, sum(count * sqrt(d2)) / boundary from the histogram, and their mean
+              (asd_mf + asd_fm) / 2; None for a sample with far > 0 (distances beyond the histogram are not known);
+      hd95    numpy.percentile(., 95) with linear interpolation of the two directions' distances pooled (MedPy's hd95), from the
+              histogram's order statistics; None when a needed rank lies in the far tail.
+    Returns {'classes': [0..K-1], 'per_class': {name: [mean over the class's samples, or None without one]}, 'mean': {name: mean over
+    the classes that have a value}, 'mean_foreground': the same without class 0, 'pairs': defined (sample, class) pairs used,
+    'undefined': pairs skipped because a map has no boundary of the class, 'far': defined pairs with far > 0}."""
+    host = lambda a: (a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)).astype(np.int64)
+    c, h = host(counts), host(hist)
+    K, B = c.shape[-3], h.shape[-1]
+    c, h = c.reshape(-1, K, 2, 3), h.reshape(-1, K, 2, B)
+    root = np.sqrt(np.arange(B, dtype=np.float64))
+    names = ('hd', 'hd95', 'asd_mf', 'asd_fm', 'assd')
+    vals = {name: [[] for _ in range(K)] for name in names}
+    pairs = undefined = far = 0
+    for n in range(c.shape[0]):
+        for k in range(K):
+            nb = c[n, k, :, 0]
+            if nb[0] == 0 or nb[1] == 0:
+                undefined += 1
+                continue
+            pairs += 1
+            vals['hd'][k].append(float(np.sqrt(float(c[n, k, :, 2].max()))))
+            pooled = np.cumsum(h[n, k].sum(0))
+            pos = 0.95 * (int(nb.sum()) - 1)                  # numpy.percentile's linear rule: the virtual index into the sorted list
+            lo = int(np.floor(pos))
+            hi = min(lo + 1, int(nb.sum()) - 1)
+            b_lo, b_hi = _order_statistic(pooled, lo), _order_statistic(pooled, hi)
+            if b_lo is not None and b_hi is not None:
+                # numpy's lerp, (1 - t) * a + t * b written as numpy writes it, so that the value is numpy.percentile's bit for bit
+                t = pos - lo
+                a, b = root[b_lo], root[b_hi]
+                vals['hd95'][k].append(float(a + (b - a) * t) if t < 0.5 else float(b - (b - a) * (1 - t)))
+            if c[n, k, :, 1].any():
+                far += 1
+                continue
+            mf, fm = (float((h[n, k, d] * root).sum()) / int(nb[d]) for d in (0, 1))
+            vals['asd_mf'][k].append(mf)
+            vals['asd_fm'][k].append(fm)
+            vals['assd'][k].append((mf + fm) / 2)
+    mean = lambda v: float(np.mean(v)) if len(v) else None
+    per_class = {name: [mean(vals[name][k]) for k in range(K)] for name in names}
+    over = lambda name, ks: mean([per_class[name][k] for k in ks if per_class[name][k] is not None])
+    return {'classes': list(range(K)), 'per_class': per_class, 'mean': {name: over(name, range(K)) for name in names},
+            'mean_foreground': {name: over(name, range(1, K)) for name in names}, 'pairs': pairs, 'undefined': undefined, 'far': far}
+
+
 def map_points(pred, grid_mode, pts, src_hw, out_hw):
     """The transformation at annotated points (nemar_map_points): pts [N,P,2] = (x, y) in pixels of the fixed image of size out_hw ->
     [N,P,2], the position in pixels of the src_hw source that the warp samples there (the continuous extension of warp_resampled's

@@ -144,6 +144,12 @@ class TestOptions(BaseOptions):
         # A.npy / B.npy alone: NEMARModel.register(similarity=True)); --bins: the joint histogram's bins per side (2 .. 64)
         a('--similarity', action='store_true')
         a('--bins', type=int, default=32)
+        # python -m nemar_amd.register: surface.json (Hausdorff distance, HD95, ASSD of the class boundaries before and after registration,
+        # from labels_A.npy / labels_B.npy: NEMARModel.register(surface=True)); --surface_max_dist D: distances below D px are
+        # histogrammed (1 .. 128), the rest counted as far; --surface_map: surface_dist2.npy, the squared distance of every boundary pixel
+        a('--surface', action='store_true')
+        a('--surface_max_dist', type=int, default=64)
+        a('--surface_map', action='store_true')
         # python -m nemar_amd.register: registered_B.npy and inverse_offsets.npy, B warped onto A by the inverse prediction
         # (NEMARModel.register(inverse=True); needs --stn_integrate K > 0).  SUPPRESS: absent from an option set that does not ask for it
         a('--inverse', action='store_true', default=argparse.SUPPRESS)

@@ -35,13 +35,23 @@ Written under --results_dir/--name/:
                               form from a --bins x --bins joint histogram of the channel means over [0, 1]; NCC, MSE and MAE; with
                               --passes K > 1 also `per_pass`, K such summaries of the network-size pair after each pass.  Needs no
                               annotation: A.npy and B.npy are enough (csrc/similarity.hip)
+    surface.json              only with --surface (needs labels_A.npy and labels_B.npy): how far the class boundaries of the two label
+                              maps are apart at labels_B.npy's size, `before` (labels_A merely resampled) and `after` registration
+                              (ops.surface_summary): per class and as class means, with and without class 0, the Hausdorff distance,
+                              its 95th percentile (HD95) and the average symmetric surface distance in pixels, averaged over the
+                              pairs where both maps hold the class, and how many (pair, class) cases were used, skipped, or reach
+                              beyond --surface_max_dist D (default 64 px: squared distances below D^2 are histogrammed, exactly);
+                              with --passes K > 1 the composite is scored (csrc/surface.hip)
+    surface_dist2.npy         only with --surface_map (which implies --surface): int32 [M,2,H,W], the squared distance at every
+                              boundary pixel of the registered label map (plane 0) and of labels_B.npy (plane 1); -1 off the
+                              boundaries, -2 where the other map has no boundary of the class
     registered_B.npy          only with --inverse (needs --stn_integrate K > 0, the flag the model was trained with, and --passes 1):
                               modality B warped onto A by the inverse prediction, in B.npy's own size, layout and dtype
     inverse_offsets.npy       only with --inverse: that prediction [M,2,h,w], exp(-v) of the velocity field the network predicted
                               (csrc/integrate.hip).  It inverts the integrated map in its true-identity convention; the slight zoom
                               of the warp's grid is not undone
 and one summary line on stdout: pairs, sizes, the scores (with --regularity: folds in per cent and SDlogJ; with --similarity:
-MI before -> after), seconds."""
+MI before -> after; with --surface: HD95 before -> after), seconds."""
 import json
 import os
 import time
@@ -147,6 +157,12 @@ def main(argv=None):
         if raw_lm[0].shape != raw_lm[1].shape:
             raise SystemExit('landmarks_A.npy %s and landmarks_B.npy %s: point pairs expected' % (raw_lm[0].shape, raw_lm[1].shape))
         lm_A, lm_B = (torch.from_numpy(np.ascontiguousarray(a).astype(np.float32)).to(device) for a in raw_lm)
+    want_surface = bool(opt.surface or opt.surface_map)
+    if want_surface and labels_B is None:
+        raise SystemExit('--surface needs labels_A.npy and labels_B.npy under %s: the boundaries of the two label maps are what it measures' % opt.dataroot)
+    if want_surface and not 1 <= opt.surface_max_dist <= ops.MAX_SURFACE_DIST:
+        raise SystemExit('--surface_max_dist %d: 1 .. %d' % (opt.surface_max_dist, ops.MAX_SURFACE_DIST))
+    surf = {'before': [], 'after': [], 'dist2': []}
     scored = {k: [] for k in ('overlap_before', 'overlap', 'tre_before_px', 'tre_px')}
     model = create_model(opt)
     model.setup(opt)
@@ -182,7 +198,13 @@ def main(argv=None):
                              labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes,
                              **(dict(regularity=True, jacobian_map=opt.jacobian_map) if want_reg else {}),
                              **(dict(similarity=True, bins=opt.bins, intensity_range=(0.0, 1.0)) if opt.similarity else {}),
-                             **(dict(inverse=True) if want_inverse else {}))
+                             **(dict(inverse=True) if want_inverse else {}),
+                             **(dict(surface=True, surface_max_dist=opt.surface_max_dist, surface_map=opt.surface_map) if want_surface else {}))
+        if want_surface:
+            surf['before'].append(out['surface']['before'])
+            surf['after'].append(out['surface']['after'])
+            if opt.surface_map:
+                surf['dist2'].append(out['surface_dist2'])
         if want_inverse:
             reg_B.append(out['registered_B'])
             inv_offsets.append(out['inverse_offsets'].clone())
@@ -238,6 +260,15 @@ def main(argv=None):
             json.dump(similarity, f, indent=1)
         if similarity['after']['mi'] is not None and similarity['before']['mi'] is not None:
             told += ', MI %.4f -> %.4f' % (similarity['before']['mi'], similarity['after']['mi'])
+    if want_surface:
+        whole = lambda pairs: ops.surface_summary(torch.cat([c for c, _ in pairs]), torch.cat([h for _, h in pairs]))
+        surface = {k: whole(surf[k]) for k in ('before', 'after')}
+        with open(os.path.join(out_dir, 'surface.json'), 'w') as f:
+            json.dump(surface, f, indent=1)
+        if opt.surface_map:
+            np.save(os.path.join(out_dir, 'surface_dist2.npy'), torch.cat(surf['dist2']).cpu().numpy())
+        hd95 = [surface[k]['mean']['hd95'] for k in ('before', 'after')]
+        told += ', HD95 %s -> %s px' % tuple('n/a' if v is None else '%.3f' % v for v in hd95)
     torch.cuda.synchronize()
     print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s%s, %.2f s -> %s'
           % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width, '' if opt.passes == 1 else ' in %d passes' % opt.passes,
