@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 612 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 613 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -117,6 +117,35 @@ int nemar_fold_penalty_fwd(const float* d, float margin, float factor, float* lo
                            size_t ws_bytes, int N, int H, int W, void* stream);
 int nemar_fold_penalty_bwd(const float* d, float margin, const float* gscale, float factor, float* gd, int accumulate, int N, int H,
                            int W, void* stream);
+
+/* Local NCC (csrc/local_ncc.hip; not a call site of the reference, whose image terms are global L1 losses): a windowed normalised
+ * cross-correlation as a differentiable loss.  x, y [N,C,H,W], planar.  win: odd window size, 3 <= win <= 11, radius r = win / 2.  For
+ * pixel p of plane (n,c) the window Omega(p) is the in-image part of the win x win square centred at p and n(p) = |Omega(p)| its pixel
+ * count: there is no zero padding, so every statistic below is invariant to a constant added to x or to y.
+ *   mx = sum_Omega x / n,  my = sum_Omega y / n
+ *   vx = max(0, sum_Omega x^2 / n - mx^2),  vy likewise,  cov = sum_Omega x y / n - mx my
+ *   cc(p) = cov^2 / (vx vy + eps)
+ * fwd: loss[0] = (accumulate ? loss[0] : 0) + factor * (1 - (1/M) sum_p cc(p)),  M = N C H W;  cc_map [N,C,H,W] = cc, or NULL.
+ *      One record per workgroup (a 64 x 16 tile of one plane) goes to the workspace, the records are merged in a fixed order: no atomics,
+ *      bitwise repeatable.  Every window is summed directly (no running window).
+ * bwd: with D = vx vy + eps and, at every pixel p,
+ *        alpha = 2 cov / D,  beta = -2 cov^2 vy / D^2,  gamma = -(alpha my + beta mx),  each divided by n(p)
+ *      (the clamp at 0 is taken as the identity it is mathematically: it only keeps D >= eps)
+ *        gx(q) (+)= -gscale[0] * factor / M * ( y(q) Box(alpha)(q) + x(q) Box(beta)(q) + Box(gamma)(q) )
+ *      Box sums over the in-image pixels within radius r of q; gscale: device scalar, the upstream gradient.  gy [N,C,H,W] or NULL: the
+ *      same with the roles of x and y swapped.  One launch, a gather: no atomics, no workspace, bitwise repeatable.
+ * The kernels subtract a constant per tile from x and y before anything is squared (the mean of the staged patch), which the definition's
+ * shift invariance allows; results therefore differ in the last bits from an evaluation of the formulas on the raw values.
+ * NEMAR_EINVAL, nothing launched: win even or outside 3..11; eps <= 0 (or NaN); a required pointer NULL (x, y, loss, workspace; x, y,
+ * gscale, gx) or any pointer not 4-byte aligned (all the alignment asked for); a non-positive N, C, H or W; N*C > 65535; H*W >= 2^31;
+ * cc_map, gx or gy overlapping x or y, gy overlapping gx; ws_bytes < nemar_local_ncc_workspace() (which is 0 for arguments the calls
+ * refuse).  Non-finite input: NEMAR_OK, NaN or Inf in the outputs that hear from it, no access outside the buffers (no index depends on
+ * the data). */
+size_t nemar_local_ncc_workspace(int N, int C, int H, int W, int win);
+int nemar_local_ncc_fwd(const float* x, const float* y, int win, float eps, float factor, float* loss, int accumulate, float* cc_map,
+                        void* workspace, size_t ws_bytes, int N, int C, int H, int W, void* stream);
+int nemar_local_ncc_bwd(const float* x, const float* y, int win, float eps, const float* gscale, float factor, float* gx, float* gy,
+                        int accumulate, int N, int C, int H, int W, void* stream);
 
 /* Scaling and squaring (csrc/integrate.hip; not in the reference, whose UNet STN warps with the network's output as it is): the network's
  * output as a stationary velocity field v, the warp reads exp(v).  One squaring step on a displacement field u [N,2,H,W], planar, in the

@@ -90,6 +90,12 @@ class NEMARModel(BaseModel):
                                      'default 0.0: switched off')
             parser.add_argument('--fold_margin', type=float, default=argparse.SUPPRESS,
                                 help='determinant below which the fold penalty acts (default 0.0: folds only; the identity has determinant ~1)')
+            # (MI355X build) train against local NCC: a windowed normalised cross-correlation of each generated image with real_B
+            # (ops.local_ncc), next to the global L1 terms.  Read like --lambda_fold: a command line without them parses as it always did
+            parser.add_argument('--lambda_lncc', type=float, default=argparse.SUPPRESS,
+                                help='weight of the local NCC terms, 1 - mean cc of fake_TR_B / fake_RT_B with real_B; default 0.0: switched off')
+            parser.add_argument('--lncc_win', type=int, default=argparse.SUPPRESS,
+                                help='window size of the local NCC terms: odd, 3 .. 11 (default 9)')
             parser.add_argument('--enable_tbvis', action='store_true',
                                 help='Enable tensorboard visualizer (default : False)')
             parser.add_argument('--multi_resolution', type=int, default=1,
@@ -112,6 +118,11 @@ class NEMARModel(BaseModel):
         if self._fold_on and opt.stn_type != 'unet':
             raise ValueError('--lambda_fold %g needs --stn_type unet: the %s STN has no fold term (theta\'s determinant is one number per '
                              'sample, not a field to regularise)' % (self._lambda_fold, opt.stn_type))
+        # the local NCC terms: two more image losses of the training step, any STN
+        self._lambda_lncc, self._lncc_win = float(getattr(opt, 'lambda_lncc', 0.0)), int(getattr(opt, 'lncc_win', 9))
+        self._lncc_on = bool(self.isTrain and self._lambda_lncc != 0.0)
+        if self._lncc_on and not (3 <= self._lncc_win <= 11 and self._lncc_win % 2 == 1):
+            raise ValueError('--lncc_win %d: the local NCC window is an odd size from 3 to 11' % self._lncc_win)
         self.setup_visualizers()
         self.tb_visualizer = None
         # T's two applications and D's 3 + 2 applications per step run as single batches: the same graph with half the launches.  (With
@@ -144,6 +155,8 @@ class NEMARModel(BaseModel):
     loss_GAN_RT = _loss_property('GAN_RT')
     loss_smoothness = _loss_property('smoothness')
     loss_fold = _loss_property('fold')
+    loss_LNCC_TR = _loss_property('LNCC_TR')
+    loss_LNCC_RT = _loss_property('LNCC_RT')
     loss_D_fake_TR = _loss_property('D_fake_TR')
     loss_D_fake_RT = _loss_property('D_fake_RT')
     loss_D = _loss_property('D')
@@ -153,6 +166,9 @@ class NEMARModel(BaseModel):
         self.loss_names = ['L1_TR', 'GAN_TR', 'L1_RT', 'GAN_RT', 'smoothness', 'D_fake_TR', 'D_fake_RT', 'D']
         if self._fold_on:
             self.loss_names.insert(self.loss_names.index('smoothness') + 1, 'fold')
+        if self._lncc_on:
+            at = self.loss_names.index('smoothness')
+            self.loss_names[at:at] = ['LNCC_TR', 'LNCC_RT']
         self.visual_names = ['real_A', 'real_B', 'fake_TR_B', 'fake_RT_B', 'registered_real_A', 'fake_B']
         self.model_names = ['T', 'R'] + (['D'] if self.isTrain else [])
 
@@ -489,8 +505,13 @@ class NEMARModel(BaseModel):
     def backward_T_and_R(self):
         opt = self.opt
         # each generated image is read by its L1 term and by the discriminators: two handles (ops.fork)
-        tr_l1, tr_d = ops.fork(self.fake_TR_B, 2)
-        rt_l1, rt_d = ops.fork(self.fake_RT_B, 2)
+        if self._lncc_on:
+            # ... and by its local NCC term: three handles
+            tr_l1, tr_d, tr_cc = ops.fork(self.fake_TR_B, 3)
+            rt_l1, rt_d, rt_cc = ops.fork(self.fake_RT_B, 3)
+        else:
+            tr_l1, tr_d = ops.fork(self.fake_TR_B, 2)
+            rt_l1, rt_d = ops.fork(self.fake_RT_B, 2)
         l1_tr = self.criterionL1(tr_l1, self.real_B, opt.lambda_recon)
         l1_rt = self.criterionL1(rt_l1, self.real_B, opt.lambda_recon)
         if self._batched:
@@ -515,6 +536,13 @@ class NEMARModel(BaseModel):
             roots.append(self.stn_fold_term)        # one more root, seeded with its weight like the smoothness term
             grads.append(self._lam_fold)
             total.append((self.stn_fold_term, self._lambda_fold))
+        if self._lncc_on:
+            # two more roots, against real_B as the L1 terms are; the weight is the kernel's factor
+            lncc = [ops.local_ncc(h, self.real_B.detach(), self._lncc_win, factor=self._lambda_lncc) for h in (tr_cc, rt_cc)]
+            self.loss_LNCC_TR, self.loss_LNCC_RT = (_LazyLoss([(t, 1.0)]) for t in lncc)
+            roots += lncc
+            grads += [self._one] * 2
+            total += [(t, 1.0) for t in lncc]
         torch.autograd.backward(roots, grads)
         return _LazyLoss(total)
 

@@ -2109,6 +2109,44 @@ def fold_penalty(d, margin=0.0, factor=1.0, return_active=False):
     return (loss, active) if return_active else loss
 
 
+class _LocalNCC(Function):
+    @staticmethod
+    def forward(ctx, x, y, win, eps, factor, want_map):
+        x, y = _c(x), _c(y)
+        N, C, H, W = x.shape
+        loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+        cc = torch.empty_like(x) if want_map else None
+        wsb = Q.local_ncc_workspace(N, C, H, W, win)
+        ws = _workspace(wsb, x.device)
+        L.local_ncc_fwd(_p(x), _p(y), win, eps, factor, _p(loss), 0, _p(cc), _p(ws), wsb, N, C, H, W, _stream())
+        ctx.save_for_backward(x, y)
+        ctx.cfg = (win, eps, factor)
+        if not want_map:
+            return loss.reshape(())
+        ctx.mark_non_differentiable(cc)
+        return loss.reshape(()), cc
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_map=None):
+        x, y = ctx.saved_tensors
+        win, eps, factor = ctx.cfg
+        N, C, H, W = x.shape
+        gx = torch.empty_like(x)
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        L.local_ncc_bwd(_p(x), _p(y), win, eps, _p(_c(g)), factor, _p(gx), _p(gy), 0, N, C, H, W, _stream())
+        return gx, gy, None, None, None, None
+
+
+def local_ncc(x, y, win=9, eps=1e-5, factor=1.0, return_map=False):
+    """factor * (1 - mean over all pixels of cc), cc the squared normalised cross-correlation of x and y [N,C,H,W] over the in-image
+    part of the win x win window around each pixel (nemar_local_ncc_fwd / _bwd; win odd, 3 .. 11) — a 0-dim device tensor with a
+    gradient towards x, and towards y when y.requires_grad.  With return_map also the cc map [N,C,H,W], no gradient.  No sync."""
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError("local_ncc: images %s and %s, expected two [N,C,H,W] of one shape" % (tuple(x.shape), tuple(y.shape)))
+    return _LocalNCC.apply(x, y, int(win), float(eps), float(factor), bool(return_map))
+
+
 def _svf_scales(steps, sign):
     """the scale each squaring step carries: sign / 2^K on the first, 1 on the others"""
     return [float(sign) / float(1 << steps)] + [1.0] * (steps - 1)
