@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 613 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 614 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -117,6 +117,36 @@ int nemar_fold_penalty_fwd(const float* d, float margin, float factor, float* lo
                            size_t ws_bytes, int N, int H, int W, void* stream);
 int nemar_fold_penalty_bwd(const float* d, float margin, const float* gscale, float factor, float* gd, int accumulate, int N, int H,
                            int W, void* stream);
+
+/* EPE loss (csrc/epe.hip; not in the reference, which has no ground-truth field): the residual nemar_registration_error measures, as a
+ * differentiable loss on the prediction the warp reads.  pred: NEMAR_GRID_UNET offsets [N,2,H,W] or NEMAR_GRID_AFFINE dtheta [N,6];
+ * g [N,2,H,W] the ground-truth field IN PIXELS, channel 0 = x.  For output pixel x = (w, h) of sample n:
+ *   S    = (ix, iy), the position the warp samples (the bits of nemar_grid_sample_fwd and nemar_registration_error)
+ *   g(S)   read bilinearly with the position clamped into the image, as nemar_registration_error reads it:
+ *          cx = min(max(ix, 0), W-1), xa = floor(cx), xb = min(xa + 1, W-1), tx = cx - xa; likewise in y
+ *   r    = (ix - w + g_x(S), iy - h + g_y(S)),   rho = sqrt(r.x^2 + r.y^2 + eps^2)     (Charbonnier; eps = 0: the meter's |r|, whose
+ *                                                                                        gradient at r = 0 is NaN)
+ * fwd: loss[0] = (accumulate ? loss[0] : 0) + factor / (N H W) * sum of rho over ALL pixels — not the meter's valid-only mean: a sample
+ *      that left the image is not excused; the clamped read extends g by its border value and the residual grows with the distance.
+ *      One float per workgroup goes to the workspace, merged in a fixed order: no atomics, bitwise repeatable.
+ * bwd: with u = r / rho and the slope of the cell floor() chose, dg/dix = (1-ty) (g01 - g00) + ty (g11 - g10) — exactly 0 where ix < 0 or
+ *      ix > W-1 (the clamp), and 0 where xa == xb — likewise in y:
+ *        Dx = u.x (1 + dx g_x) + u.y dx g_y,   Dy = u.x dy g_x + u.y (1 + dy g_y),   k = gscale[0] * factor / (N H W)
+ *      (gscale: device scalar, the upstream gradient).
+ *      UNET:   gpred[n,0,h,w] (+)= k (W/2) Dx,  gpred[n,1,h,w] (+)= k (H/2) Dy — one gather launch that does not touch the workspace.
+ *      AFFINE: gpred[n,0..5] (+)= k * sum over (h,w) of [(W/2) Dx (xb, yb, 1), (H/2) Dy (xb, yb, 1)], xb = (2w+1)/W - 1, yb = (2h+1)/H - 1
+ *              (affine_grid's base coordinates); one 6-vector per workgroup goes to the workspace, merged in a fixed order.
+ *      No atomics in either: bitwise repeatable.
+ * NEMAR_EINVAL, nothing launched, outputs untouched: a pointer NULL or not 4-byte aligned (all the alignment asked for; both calls want
+ * the workspace, whichever mode); a grid_mode other than the two; a non-positive N, H or W; N > 65535; H*W >= 2^31;
+ * ws_bytes < nemar_epe_loss_workspace(); gpred equal to pred; eps < 0 or not finite.
+ * Non-finite data: NEMAR_OK, and NaN or Inf in exactly what hears from it — the loss; for UNET the two gradient elements of a pixel whose
+ * offsets or whose four read texels of g hold it; for AFFINE the six of a sample.  No address depends on it. */
+size_t nemar_epe_loss_workspace(int N, int H, int W);
+int nemar_epe_loss_fwd(const float* pred, int grid_mode, const float* g, float eps, float factor, float* loss, int accumulate,
+                       void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+int nemar_epe_loss_bwd(const float* pred, int grid_mode, const float* g, float eps, const float* gscale, float factor, float* gpred,
+                       int accumulate, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
 
 /* Local NCC (csrc/local_ncc.hip; not a call site of the reference, whose image terms are global L1 losses): a windowed normalised
  * cross-correlation as a differentiable loss.  x, y [N,C,H,W], planar.  win: odd window size, 3 <= win <= 11, radius r = win / 2.  For

@@ -45,6 +45,9 @@ SIGNATURES = {
     "nemar_fold_penalty_workspace": (_sz, [_i, _i, _i]),
     "nemar_fold_penalty_fwd": (_i, [_vp, _fl, _fl, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_fold_penalty_bwd": (_i, [_vp, _fl, _vp, _fl, _vp, _i, _i, _i, _i, _vp]),
+    "nemar_epe_loss_workspace": (_sz, [_i, _i, _i]),
+    "nemar_epe_loss_fwd": (_i, [_vp, _i, _vp, _fl, _fl, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
+    "nemar_epe_loss_bwd": (_i, [_vp, _i, _vp, _fl, _vp, _fl, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_local_ncc_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "nemar_local_ncc_fwd": (_i, [_vp, _vp, _i, _fl, _fl, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "nemar_local_ncc_bwd": (_i, [_vp, _vp, _i, _fl, _vp, _fl, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

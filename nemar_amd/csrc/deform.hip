@@ -14,6 +14,7 @@
 // per lane otherwise.  No floating-point atomics: the meter's sums are per-workgroup partials merged in a fixed order, so every
 // result is bitwise repeatable.
 #include "common.h"
+#include "clamped_bilerp.h"
 #include "warp_grid.h"
 
 namespace {
@@ -91,25 +92,7 @@ __global__ __launch_bounds__(256) void deform_field_kernel(const float* __restri
     }
 }
 
-// ---- bilinear read with border clamp (shared by the sampler and the meter) ------------------------------------------------------
-struct Corner {
-    int xa, xb, ya, yb;      // the two columns / rows, inside [0, W-1] / [0, H-1]
-    float tx, ty;
-};
-// position (px, py) clamped into [0, W-1] x [0, H-1] (fmaxf / fminf drop a NaN: the address stays inside whatever the field holds)
-__device__ __forceinline__ Corner clamp_locate(float px, float py, int W, int H) {
-    const float cx = fminf(fmaxf(px, 0.f), (float)(W - 1)), cy = fminf(fmaxf(py, 0.f), (float)(H - 1));
-    const float fx = floorf(cx), fy = floorf(cy);
-    Corner k;
-    k.xa = (int)fx; k.ya = (int)fy;
-    k.xb = min(k.xa + 1, W - 1); k.yb = min(k.ya + 1, H - 1);
-    k.tx = cx - fx; k.ty = cy - fy;
-    return k;
-}
-__device__ __forceinline__ float bilerp(float a, float b, float c, float d, float tx, float ty) {
-    const float ex = 1.f - tx, ey = 1.f - ty;
-    return a * (ex * ey) + b * (tx * ey) + c * (ex * ty) + d * (tx * ty);
-}
+// (the bilinear read with border clamp that the sampler and the meter share — clamp_locate, bilerp — and warp_position: clamped_bilerp.h)
 
 // ---- (b) crop + flip + deform + normalise ------------------------------------------------------------------------------------------
 // y[b][c][q] = (F_b(q + g_b(q)) * scale - 0.5) / 0.5, F_b = the cropped-and-flipped image of crop_flip_normalize_kernel read bilinearly
@@ -213,15 +196,6 @@ __device__ __forceinline__ void reg_block_store(const RegAcc& a, unsigned* __res
             dst[4] = fold; dst[5] = interior;
         }
     }
-}
-
-// x -> S(x): the pixel position the warp kernel samples for grid_src values (sx, sy) held in registers, at output pixel (h, w)
-// (RegSrc: warp_grid.h)
-template <int MODE>
-__device__ __forceinline__ void warp_position(float sx, float sy, int h, int w, int H, int W, const float* th, float& ix, float& iy) {
-    float gx, gy;
-    grid_coord<MODE>(RegSrc{sx, sy}, h, w, H, W, th, gx, gy);
-    sample_position(gx, gy, W, H, ix, iy);
 }
 
 template <int MODE, int VEC>
@@ -329,17 +303,7 @@ __global__ __launch_bounds__(256) void registration_error_merge_kernel(const uns
     reg_block_store(acc, reinterpret_cast<unsigned*>(out + (size_t)n * 6), red, redu, true);
 }
 
-// workgroups per sample: enough to cover the sample one pixel per lane, at most 256 CUs x 8 over the batch
-int reg_blocks(int N, long long items) {
-    int gx = nemar_cdiv(items, 256);
-    const int cap = nemar_cdiv(256 * 8, N);
-    if (gx > cap) gx = cap;
-    return gx < 1 ? 1 : gx;
-}
-
-bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
+// (reg_blocks, aligned16: clamped_bilerp.h)
 
 }  // namespace
 

@@ -96,6 +96,13 @@ class NEMARModel(BaseModel):
                                 help='weight of the local NCC terms, 1 - mean cc of fake_TR_B / fake_RT_B with real_B; default 0.0: switched off')
             parser.add_argument('--lncc_win', type=int, default=argparse.SUPPRESS,
                                 help='window size of the local NCC terms: odd, 3 .. 11 (default 9)')
+            # (MI355X build) train against known misalignment: the registration error of batches that carry a ground-truth field
+            # (--misalign), as a loss on the prediction the warp reads (ops.epe_loss).  Read like --lambda_fold
+            parser.add_argument('--lambda_epe', type=float, default=argparse.SUPPRESS,
+                                help='weight of the supervised registration term, mean sqrt(|r|^2 + epe_eps^2) of the residual r against '
+                                     'the known misalignment (needs --misalign affine|elastic|both); default 0.0: switched off')
+            parser.add_argument('--epe_eps', type=float, default=argparse.SUPPRESS,
+                                help='Charbonnier epsilon of the supervised registration term in pixels, > 0 (default 0.01)')
             parser.add_argument('--enable_tbvis', action='store_true',
                                 help='Enable tensorboard visualizer (default : False)')
             parser.add_argument('--multi_resolution', type=int, default=1,
@@ -123,6 +130,11 @@ class NEMARModel(BaseModel):
         self._lncc_on = bool(self.isTrain and self._lambda_lncc != 0.0)
         if self._lncc_on and not (3 <= self._lncc_win <= 11 and self._lncc_win % 2 == 1):
             raise ValueError('--lncc_win %d: the local NCC window is an odd size from 3 to 11' % self._lncc_win)
+        # the supervised registration term: one more loss of the training step on batches that carry a gt_field, any STN
+        self._lambda_epe, self._epe_eps = float(getattr(opt, 'lambda_epe', 0.0)), float(getattr(opt, 'epe_eps', 0.01))
+        self._epe_on = bool(self.isTrain and self._lambda_epe != 0.0)
+        if self._epe_on and not self._epe_eps > 0.0:
+            raise ValueError('--epe_eps %g: the Charbonnier epsilon of --lambda_epe must be positive' % self._epe_eps)
         self.setup_visualizers()
         self.tb_visualizer = None
         # T's two applications and D's 3 + 2 applications per step run as single batches: the same graph with half the launches.  (With
@@ -148,6 +160,8 @@ class NEMARModel(BaseModel):
             self._lam_smooth = torch.full((), float(opt.lambda_smooth), dtype=torch.float32, device=self.device)
             if self._fold_on:
                 self._lam_fold = torch.full((), self._lambda_fold, dtype=torch.float32, device=self.device)
+            if self._epe_on:
+                self._lam_epe = torch.full((), self._lambda_epe, dtype=torch.float32, device=self.device)
 
     loss_L1_TR = _loss_property('L1_TR')
     loss_GAN_TR = _loss_property('GAN_TR')
@@ -155,6 +169,7 @@ class NEMARModel(BaseModel):
     loss_GAN_RT = _loss_property('GAN_RT')
     loss_smoothness = _loss_property('smoothness')
     loss_fold = _loss_property('fold')
+    loss_EPE = _loss_property('EPE')
     loss_LNCC_TR = _loss_property('LNCC_TR')
     loss_LNCC_RT = _loss_property('LNCC_RT')
     loss_D_fake_TR = _loss_property('D_fake_TR')
@@ -166,6 +181,8 @@ class NEMARModel(BaseModel):
         self.loss_names = ['L1_TR', 'GAN_TR', 'L1_RT', 'GAN_RT', 'smoothness', 'D_fake_TR', 'D_fake_RT', 'D']
         if self._fold_on:
             self.loss_names.insert(self.loss_names.index('smoothness') + 1, 'fold')
+        if self._epe_on:
+            self.loss_names.insert(self.loss_names.index('fold' if self._fold_on else 'smoothness') + 1, 'EPE')
         if self._lncc_on:
             at = self.loss_names.index('smoothness')
             self.loss_names[at:at] = ['LNCC_TR', 'LNCC_RT']
@@ -396,16 +413,40 @@ class NEMARModel(BaseModel):
         return levels is not None and h % (1 << levels) == 0 and w % (1 << levels) == 0 and min(h, w) >= (1 << levels)
 
     # ---- forward -------------------------------------------------------------------------------------------
+    def _fork_prediction(self, n_warps):
+        """netR's prediction for the set_input pair as handles (netR.fork_field): one per warp, the regulariser's, and — None where the
+        term is off — the fold term's and the EPE term's"""
+        kw = {}
+        if self._fold_on:
+            kw['fold'] = True
+        if self._epe_on:
+            kw['extra'] = 1
+        out = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), n_warps, **kw)
+        return out[0], out[1], (out[2] if self._fold_on else None), (out[-1][0] if self._epe_on else None)
+
+    def _further_stn_terms(self, f_fold, f_epe):
+        if self._fold_on:
+            self.stn_fold_term = self.netR.fold_term(f_fold, self._fold_margin)
+        if self._epe_on:
+            gt = getattr(self, 'gt_field', None)
+            if gt is None:
+                raise RuntimeError('--lambda_epe %g: the current batch carries no gt_field to train against (train with --misalign '
+                                   'affine|elastic|both)' % self._lambda_epe)
+            want = (self.real_A.size(0), 2, self.real_A.size(2), self.real_A.size(3))
+            if tuple(gt.shape) != want:
+                raise ValueError('--lambda_epe: gt_field %s is not the size of the prediction, %s' % (tuple(gt.shape), want))
+            self.stn_epe_term = self.netR.epe_term(f_epe, gt, self._epe_eps)
+
     def forward(self):
         if not self._batched:
             # the reference's own order (models/nemar_model.py:161-176)
             self.fake_B = self.netT(self.real_A)
-            if self._fold_on:
-                # netR.forward() piece by piece, with one more handle of the field for the fold term
-                (f_warp,), f_reg, f_fold = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 1, fold=True)
+            if self._fold_on or self._epe_on:
+                # netR.forward() piece by piece, with one more handle of the field for each further term
+                (f_warp,), f_reg, f_fold, f_epe = self._fork_prediction(1)
                 warped = self.netR.warp(f_warp, [self.real_A, self.fake_B])
                 reg_term = self.netR.regularization(f_reg, warped[0])
-                self.stn_fold_term = self.netR.fold_term(f_fold, self._fold_margin)
+                self._further_stn_terms(f_fold, f_epe)
             else:
                 warped, reg_term = self.netR(self.real_A, self.real_B, apply_on=[self.real_A, self.fake_B])
             self.stn_reg_term = reg_term
@@ -420,10 +461,7 @@ class NEMARModel(BaseModel):
             n = self.real_A.size(0)
             # (the field has three consumers — two warps and the regulariser —, the batch of T two sources and two slices: the library's own
             # nodes for fan-out, concatenation and slicing, ops.fork / cat_batch / split_batch, instead of autograd's ATen kernels)
-            if self._fold_on:
-                (f_a, f_b), f_reg, f_fold = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 2, fold=True)
-            else:
-                (f_a, f_b), f_reg = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), 2)
+            (f_a, f_b), f_reg, f_fold, f_epe = self._fork_prediction(2)
             self.registered_real_A = self.netR.warp(f_a, [self.real_A])[0]
             # (only the second half is differentiated: the stem's data gradient runs on it alone)
             with ops.norm_segments(2):
@@ -431,8 +469,7 @@ class NEMARModel(BaseModel):
             self.fake_B, self.fake_TR_B = ops.split_batch(both, 2)
             self.fake_RT_B = self.netR.warp(f_b, [self.fake_B])[0]
             self.stn_reg_term = self.netR.regularization(f_reg, self.registered_real_A)
-            if self._fold_on:
-                self.stn_fold_term = self.netR.fold_term(f_fold, self._fold_margin)
+            self._further_stn_terms(f_fold, f_epe)
         self._resized = {}
         if self.tb_visualizer is not None:
             # the reference runs netR a second time here (get_grid, :172-173); the field of the pass above is the same tensor
@@ -536,6 +573,11 @@ class NEMARModel(BaseModel):
             roots.append(self.stn_fold_term)        # one more root, seeded with its weight like the smoothness term
             grads.append(self._lam_fold)
             total.append((self.stn_fold_term, self._lambda_fold))
+        if self._epe_on:
+            self.loss_EPE = _LazyLoss([(self.stn_epe_term, self._lambda_epe)])
+            roots.append(self.stn_epe_term)         # likewise
+            grads.append(self._lam_epe)
+            total.append((self.stn_epe_term, self._lambda_epe))
         if self._lncc_on:
             # two more roots, against real_B as the L1 terms are; the weight is the kernel's factor
             lncc = [ops.local_ncc(h, self.real_B.detach(), self._lncc_win, factor=self._lambda_lncc) for h in (tr_cc, rt_cc)]
@@ -558,7 +600,15 @@ class NEMARModel(BaseModel):
             raise RuntimeError('enable_step_graph: disable the tensorboard visualiser (it reads tensors between launches)')
         ops.step_params(True, self.device)
         self._static_A, self._static_B = self.real_A.clone(), self.real_B.clone()
-        opts = [self.optimizer_D, self.optimizer_R, self.optimizer_T]
+        # the EPE term reads the batch's ground-truth field inside the captured step: a static buffer like the two images'
+        self._static_gt = None
+        if self._epe_on:
+            if getattr(self, 'gt_field', None) is None:
+                raise RuntimeError('enable_step_graph: --lambda_epe %g and the current batch carries no gt_field (train with --misalign '
+                                   'affine|elastic|both)' % self._lambda_epe)
+            self._static_gt = self.gt_field.clone()
+            self.gt_field = self._static_gt
+        opts =[self.optimizer_D, self.optimizer_R, self.optimizer_T]
         # The warm-up steps must not train: they run with lr = 0 (Adam leaves every parameter bit-unchanged: p - 0 * x) and the
         # moments, step counts and the dropout step counter are put back afterwards — the first replay is then step 1 of the same
         # schedule an eager loop would follow, on untouched weights.  (The packed-weight images are rebuilt from the same values, so
@@ -609,7 +659,9 @@ class NEMARModel(BaseModel):
         ops.pin_workspaces(True)          # the graph holds their addresses: from now on they may grow but are never freed
 
     def _replay_step(self):
-        if self.real_A.shape != self._static_A.shape or self.real_B.shape != self._static_B.shape:
+        static_gt = getattr(self, '_static_gt', None)
+        gt_fits = static_gt is None or (getattr(self, 'gt_field', None) is not None and self.gt_field.shape == static_gt.shape)
+        if self.real_A.shape != self._static_A.shape or self.real_B.shape != self._static_B.shape or not gt_fits:
             # a batch of another shape (the ragged last batch of an epoch): the captured launches do not describe it — run this step
             # eagerly, in the same device-parameter mode (bit-identical arithmetic), and keep the graph for the next full batch
             ops.begin_step()
@@ -618,6 +670,9 @@ class NEMARModel(BaseModel):
             self._static_A.copy_(self.real_A)
             self._static_B.copy_(self.real_B)
             self.real_A, self.real_B = self._static_A, self._static_B
+        if static_gt is not None and self.gt_field is not static_gt:
+            static_gt.copy_(self.gt_field)
+            self.gt_field = static_gt
         ops.begin_step()
         for o in (self.optimizer_D, self.optimizer_R, self.optimizer_T):
             o.prepare_step(o.step_count + 1)

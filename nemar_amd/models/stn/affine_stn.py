@@ -135,10 +135,17 @@ class AffineSTN(nn.Module):
         """what last_prediction() returns from now on: a composite made outside the forward pass (NEMARModel.cascade)"""
         self.last_dtheta = dtheta.detach()
 
-    def fork_field(self, field, n_warps):
-        """-> ([one theta handle per warp() call], the handle for regularization()) — ops.fork, as UnetSTN.fork_field"""
-        hs = ops.fork(field, n_warps + 1)
-        return list(hs[:n_warps]), hs[n_warps]
+    def fork_field(self, field, n_warps, extra=0):
+        """-> ([one theta handle per warp() call], the handle for regularization()) — ops.fork, as UnetSTN.fork_field; with
+        extra = k > 0 a last element: a list of k more handles, one per further consumer (epe_term())"""
+        hs = ops.fork(field, n_warps + 1 + int(extra))
+        out = list(hs[:n_warps]), hs[n_warps]
+        return (*out, list(hs[n_warps + 1:])) if extra else out
+
+    def epe_term(self, field, gt_field, eps=0.01):
+        """mean over all pixels of sqrt(|r|^2 + eps^2), r the residual registration_error measures against the ground-truth field
+        gt_field [N,2,h,w] in pixels, for the sampling positions of affine_grid(theta) at the field's size (ops.epe_loss)"""
+        return ops.epe_loss(field, ops.GRID_AFFINE, gt_field, eps, 1.0)
 
     def regularization(self, field, warped_first=None):
         return self._calculate_regularization_term(field)

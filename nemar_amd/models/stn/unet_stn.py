@@ -220,19 +220,24 @@ class UnetSTN(nn.Module):
         self.last_offsets = offsets.detach()
         self.last_velocity = None                  # a composite is the exponential of no single velocity: it has no inverse_prediction()
 
-    def fork_field(self, field, n_warps, fold=False):
+    def fork_field(self, field, n_warps, fold=False, extra=0):
         """-> ([one field per warp() call], the field for regularization()): handles of the same tensors (ops.fork), so that the
         consumers' gradients are added by the library's kernel instead of autograd's accumulation.  With fold=True a third element:
-        one more handle of the field the warp reads, for fold_term()."""
+        one more handle of the field the warp reads, for fold_term().  With extra = k > 0 a last element: a list of k more such
+        handles, one per further consumer of the field the warp reads (epe_term())."""
         d, d_up = field
-        extra = 1 if fold else 0
+        more = (1 if fold else 0) + int(extra)
         if d_up is d:
-            hs = ops.fork(d, n_warps + 1 + extra)
+            hs = ops.fork(d, n_warps + 1 + more)
             out = [(h, h) for h in hs[:n_warps]], (hs[n_warps], hs[n_warps])
-            return (*out, (hs[n_warps + 1], hs[n_warps + 1])) if fold else out
-        ups = ops.fork(d_up, n_warps + extra)
-        out = [(d, u) for u in ups[:n_warps]], (d, d_up)
-        return (*out, (d, ups[n_warps])) if fold else out
+            rest = [(h, h) for h in hs[n_warps + 1:]]
+        else:
+            ups = ops.fork(d_up, n_warps + more)
+            out = [(d, u) for u in ups[:n_warps]], (d, d_up)
+            rest = [(d, u) for u in ups[n_warps:]]
+        if fold:
+            out = (*out, rest.pop(0))
+        return (*out, rest) if extra else out
 
     def fold_term(self, field, margin=0.0):
         """mean over the interior pixels of max(0, margin - det) on the field the warp reads (ops.fold_penalty: the Jacobian
@@ -242,6 +247,12 @@ class UnetSTN(nn.Module):
         self.last_fold_active = active
         self.last_fold_interior = (field[1].size(2) - 1) * (field[1].size(3) - 1)      # per sample: what the counts are a share of
         return term
+
+    def epe_term(self, field, gt_field, eps=0.01):
+        """mean over all pixels of sqrt(|r|^2 + eps^2), r the residual registration_error measures against the ground-truth field
+        gt_field [N,2,oh,ow] in pixels (ops.epe_loss), on the field the warp reads — past the integration and the low-resolution
+        resize, where fold_term() acts."""
+        return ops.epe_loss(field[1], ops.GRID_UNET, gt_field, eps, 1.0)
 
     def regularization(self, field, warped_first):
         return self._calculate_regularization_term(field[0], warped_first)

@@ -2109,6 +2109,50 @@ def fold_penalty(d, margin=0.0, factor=1.0, return_active=False):
     return (loss, active) if return_active else loss
 
 
+class _EpeLoss(Function):
+    @staticmethod
+    def forward(ctx, pred, mode, g, eps, factor):
+        pred, g = _c(pred), _c(g)
+        N, _, H, W = g.shape
+        loss = torch.empty((1,), dtype=torch.float32, device=g.device)
+        wsb = Q.epe_loss_workspace(N, H, W)
+        ws = _workspace(wsb, g.device)
+        L.epe_loss_fwd(_p(pred), mode, _p(g), eps, factor, _p(loss), 0, _p(ws), wsb, N, H, W, _stream())
+        ctx.save_for_backward(pred, g)
+        ctx.cfg = (mode, eps, factor)
+        return loss.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        pred, g = ctx.saved_tensors
+        mode, eps, factor = ctx.cfg
+        N, _, H, W = g.shape
+        gpred = torch.empty_like(pred)
+        wsb = Q.epe_loss_workspace(N, H, W)
+        ws = _workspace(wsb, g.device)
+        L.epe_loss_bwd(_p(pred), mode, _p(g), eps, _p(_c(gout)), factor, _p(gpred), 0, _p(ws), wsb, N, H, W, _stream())
+        return gpred, None, None, None, None
+
+
+def epe_loss(pred, grid_mode, gt_field, eps=0.01, factor=1.0):
+    """factor * mean over ALL pixels of sqrt(|r|^2 + eps^2), r = S(x) + g(S(x)) - x the residual registration_error measures: S the
+    position the warp samples for the prediction pred (GRID_UNET: offsets [N,2,H,W]; GRID_AFFINE: dtheta [N,6]), g = gt_field [N,2,H,W]
+    in pixels read bilinearly there, border-clamped (nemar_epe_loss_fwd / _bwd) — a 0-dim device tensor with a gradient towards pred
+    only.  A sample that leaves the image is not excused, unlike the meter's epe_px.  No sync."""
+    if gt_field.dim() != 4 or gt_field.shape[1] != 2:
+        raise ValueError("epe_loss: ground-truth field %s, expected [N,2,H,W]" % (tuple(gt_field.shape),))
+    N, _, H, W = gt_field.shape
+    if grid_mode not in (GRID_UNET, GRID_AFFINE):
+        raise ValueError("epe_loss: grid mode %r (GRID_UNET or GRID_AFFINE)" % (grid_mode,))
+    want = (N, 2, H, W) if grid_mode == GRID_UNET else (N, 6)
+    if tuple(pred.shape) != want:
+        raise ValueError("epe_loss: prediction %s, expected %s for a field %s" % (tuple(pred.shape), want, tuple(gt_field.shape)))
+    if not float(eps) > 0.0:
+        raise ValueError("epe_loss: eps %r must be positive (at eps = 0 the gradient of a zero residual is NaN)" % (eps,))
+    return _EpeLoss.apply(pred, int(grid_mode), gt_field.detach(), float(eps), float(factor))
+
+
 class _LocalNCC(Function):
     @staticmethod
     def forward(ctx, x, y, win, eps, factor, want_map):
