@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 614 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 615 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -147,6 +147,45 @@ int nemar_epe_loss_fwd(const float* pred, int grid_mode, const float* g, float e
                        void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
 int nemar_epe_loss_bwd(const float* pred, int grid_mode, const float* g, float eps, const float* gscale, float factor, float* gpred,
                        int accumulate, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+
+/* Soft-Dice loss (csrc/dice.hip; not in the reference, which has no labels): the Dice nemar_label_overlap reports, as a differentiable loss
+ * on the prediction the warp reads.  pred: NEMAR_GRID_UNET offsets [N,2,H,W] or NEMAR_GRID_AFFINE dtheta [N,6]; labels_moving and
+ * labels_fixed [N,H,W]: float class ids by nemar_label_overlap's rule (k iff the value == (float)k for an integer 0 <= k < K, anything
+ * else — negative, >= K, fractional, NaN, Inf — is no class).  For output pixel x of sample n:
+ *   S      = (ix, iy), the position the warp samples (the bits of nemar_grid_sample_fwd), x0 = floor(ix), tx = ix - x0, likewise in y;
+ *   p_k(x) = the sum of the bilinear weights (1-tx)(1-ty), tx(1-ty), (1-tx)ty, tx ty of those of the four corners (y0,x0), (y0,x0+1),
+ *            (y0+1,x0), (y0+1,x0+1) that lie INSIDE the image (zeros padding, as the image warp) and whose class in labels_moving is k;
+ *   f_k(x) = [class of labels_fixed[x] == k];
+ *   per sample and class  I = sum_x p_k f_k,  M = sum_x p_k,  F = sum_x f_k;
+ *   dice = (2 I + eps) / (M + F + eps), eps > 0 in pixels;
+ *   loss = factor / (N Kc) * sum_n sum_{k >= k0} (1 - dice), k0 = 0 or 1 (1 leaves the background class 0 out), Kc = K - k0.
+ * A class absent from both maps has dice 1 and gradient 0; the denominator does not depend on the data.
+ * A pixel whose ix or iy is NOT FINITE contributes nothing to I and M and gets gradient exactly 0 (its f_k still counts) — unlike
+ * nemar_epe_loss_*, which is NaN where it hears from one: the sums are integers and cannot carry a NaN.  No address depends on the data
+ * beyond the clamped corner reads.
+ * nemar_dice_sums: sums [N,K,3] uint64 = I and M in fixed point with 30 fractional bits (every corner weight rounded once to nearest,
+ *      then added as an integer: H W < 2^31 pixels of total weight <= 1 plus four half-unit roundings stay below 2^63), F a plain pixel
+ *      count.  Integer atomics: independent of the order of arrival, bitwise repeatable, the same bits for aligned and unaligned tensors.
+ * nemar_dice_loss_fwd: the sums, then one finalising workgroup that converts them in double, adds the terms in a fixed order,
+ *      loss[0] = (accumulate ? loss[0] : 0) + loss, and writes coef [N,K,2] float for the backward: with D = M + F + eps, c = factor / (N Kc),
+ *      a = -2 c / D, b = c (2 I + eps) / D^2 (both 0 for k < k0), so that dL/dp_k(x) = a f_k(x) + b.
+ * nemar_dice_loss_bwd: a gather that reads coef and does not repeat the sums.  Per pixel q_c = a[k_c] [k_c == kf] + b[k_c] for the four
+ *      corners (0 outside the image or of no class), dL/dix = (1-ty)(q01 - q00) + ty (q11 - q10), dL/diy = (1-tx)(q10 - q00) + tx (q11 - q01):
+ *      the slope of the cell floor() chose.  gscale: device scalar, the upstream gradient.
+ *      UNET:   gpred[n,0,h,w] (+)= gscale[0] (W/2) dL/dix,  gpred[n,1,h,w] (+)= gscale[0] (H/2) dL/diy — one launch, no workspace use.
+ *      AFFINE: gpred[n,0..5] (+)= gscale[0] * sum over (h,w) of [(W/2) dL/dix (xb, yb, 1), (H/2) dL/diy (xb, yb, 1)], (xb, yb) affine_grid's
+ *              base coordinates; one 6-vector per workgroup goes to the workspace, merged in a fixed order.  No float atomics anywhere.
+ * NEMAR_EINVAL, nothing launched, outputs untouched: a pointer NULL or not 4-byte aligned (sums: 8-byte); a grid_mode other than the two;
+ * K outside 1 .. 1024; k0 not 0 or 1, or k0 >= K; eps not finite or <= 0; a non-positive N, H or W; N > 65535; H*W >= 2^31;
+ * ws_bytes < nemar_dice_loss_workspace(); gpred equal to pred. */
+size_t nemar_dice_loss_workspace(int N, int H, int W);
+int nemar_dice_sums(const float* pred, int grid_mode, const float* labels_moving, const float* labels_fixed, unsigned long long* sums,
+                    int N, int K, int H, int W, void* stream);
+int nemar_dice_loss_fwd(const float* pred, int grid_mode, const float* labels_moving, const float* labels_fixed, int K, int k0, float eps,
+                        float factor, float* loss, int accumulate, unsigned long long* sums, float* coef, int N, int H, int W, void* stream);
+int nemar_dice_loss_bwd(const float* pred, int grid_mode, const float* labels_moving, const float* labels_fixed, const float* coef, int K,
+                        const float* gscale, float* gpred, int accumulate, void* workspace, size_t ws_bytes, int N, int H, int W,
+                        void* stream);
 
 /* Local NCC (csrc/local_ncc.hip; not a call site of the reference, whose image terms are global L1 losses): a windowed normalised
  * cross-correlation as a differentiable loss.  x, y [N,C,H,W], planar.  win: odd window size, 3 <= win <= 11, radius r = win / 2.  For
@@ -547,6 +586,12 @@ int nemar_deform_field(const float* params, float* g, int B, int Hc, int Wc, int
  * for bit. */
 int nemar_crop_flip_deform_normalize(const float* pool, const int* params, const float* g, float* y, int M, int B, int C,
                                      int H, int W, int Hc, int Wc, float scale, void* stream);
+/* The label twin of nemar_crop_flip_deform_normalize: pool [M,1,H,W] float class ids, the same params (crop window, flip) and the same
+ * positions q + g(q) clamped to the crop window, read by NEAREST sampling — round half to even, the rounding of
+ * nemar_warp_resampled_fwd(NEMAR_SAMPLE_NEAREST) — and copied: no blending, no normalisation.  y [B,1,Hc,Wc].  g == NULL is the plain
+ * crop / flip copy, and so is g == 0. */
+int nemar_crop_flip_deform_labels(const float* pool, const int* params, const float* g, float* y, int M, int B, int H, int W, int Hc,
+                                  int Wc, void* stream);
 /* The meter.  pred is the STN's prediction as nemar_grid_sample_fwd takes it: NEMAR_GRID_UNET offsets [N,2,H,W] or NEMAR_GRID_AFFINE
  * dtheta [N,6].  S(x) = the pixel position that kernel samples for output pixel x; the registered image is A'(S(x)) =
  * A(S(x) + g(S(x))), so the residual is r(x) = S(x) + g(S(x)) - x, g read bilinearly at S(x); |.| is the Euclidean length.

@@ -48,6 +48,10 @@ SIGNATURES = {
     "nemar_epe_loss_workspace": (_sz, [_i, _i, _i]),
     "nemar_epe_loss_fwd": (_i, [_vp, _i, _vp, _fl, _fl, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_epe_loss_bwd": (_i, [_vp, _i, _vp, _fl, _vp, _fl, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
+    "nemar_dice_loss_workspace": (_sz, [_i, _i, _i]),
+    "nemar_dice_sums": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "nemar_dice_loss_fwd": (_i, [_vp, _i, _vp, _vp, _i, _i, _fl, _fl, _vp, _i, _vp, _vp, _i, _i, _i, _vp]),
+    "nemar_dice_loss_bwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_local_ncc_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "nemar_local_ncc_fwd": (_i, [_vp, _vp, _i, _fl, _fl, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "nemar_local_ncc_bwd": (_i, [_vp, _vp, _i, _fl, _vp, _fl, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -110,6 +114,7 @@ SIGNATURES = {
     "nemar_crop_flip_normalize": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _fl, _vp]),
     "nemar_deform_field": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "nemar_crop_flip_deform_normalize": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _fl, _vp]),
+    "nemar_crop_flip_deform_labels": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_registration_error_workspace": (_sz, [_i, _i, _i]),
     "nemar_registration_error": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_warp_resampled_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),

@@ -7,6 +7,7 @@
 // is A'(q) = A_crop(q + g(q)).
 //   nemar_deform_field                 g from per-sample parameters: affine about the crop centre + cubic B-spline lattice
 //   nemar_crop_flip_deform_normalize   nemar_crop_flip_normalize sampling bilinearly at q + g(q), border-clamped
+//   nemar_crop_flip_deform_labels      its label twin: the same window, flip and positions, nearest sampling, class ids copied
 //   nemar_registration_error           residual r(x) = S(x) + g(S(x)) - x of the warp's own sampling position S(x) (warp_grid.h)
 //
 // All three are HBM-bound streaming kernels (8 B/px written; 8 + 4C B/px + gathers; 16 B/px read): one lane owns VEC consecutive
@@ -148,6 +149,57 @@ __global__ __launch_bounds__(256) void crop_flip_deform_normalize_kernel(const f
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) q[v] = r[v];
             }
+        }
+    }
+}
+
+// ---- (b') crop + flip + deform of a label map ------------------------------------------------------------------------------------------
+// The label twin of crop_flip_deform_normalize_kernel: pool [M,1,H,W] float class ids, the same crop window and flip, the same positions
+// q + g(q) clamped to the crop window — read by NEAREST sampling, round half to even (rintf: the rounding of taps_at<SAMPLE_NEAREST>,
+// resampled_grid.h), and copied: a class id is never blended and never normalised.  DEFORM false (g == NULL): the plain crop / flip copy,
+// which g == 0 gives too (rintf of an integer is the integer).  fmaxf / fminf drop a NaN: every address is in the crop window.
+template <int VEC, bool DEFORM>
+__global__ __launch_bounds__(256) void crop_flip_deform_labels_kernel(const float* __restrict__ pool, const int* __restrict__ params,
+                                                                      const float* __restrict__ g, float* __restrict__ y, int M, int H, int W,
+                                                                      int Hc, int Wc) {
+    const int b = blockIdx.y;
+    const int4 pr = reinterpret_cast<const int4*>(params)[b];
+    const int idx = min(max(pr.x, 0), M - 1), y0 = min(max(pr.y, 0), H - Hc), x0 = min(max(pr.z, 0), W - Wc);
+    const bool flip = pr.w != 0;
+    const size_t cplane = (size_t)Hc * Wc, pplane = (size_t)H * W;
+    const float* gN = DEFORM ? g + (size_t)b * 2 * cplane : nullptr;
+    float* yN = y + (size_t)b * cplane;
+    const float* src = pool + (size_t)idx * pplane + (size_t)y0 * W;     // row y0 of the map
+    const int wq = Wc / VEC, items = Hc * wq;
+    for (int it = blockIdx.x * blockDim.x + threadIdx.x; it < items; it += gridDim.x * blockDim.x) {
+        const int h = it / wq;
+        const int w0 = (it - h * wq) * VEC;
+        const size_t o = (size_t)h * Wc + w0;
+        float gx[VEC], gy[VEC], r[VEC];
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) { gx[v] = 0.f; gy[v] = 0.f; }
+        if (DEFORM) {
+            if (VEC == 4) {
+                const float4 a = *reinterpret_cast<const float4*>(gN + o), c = *reinterpret_cast<const float4*>(gN + cplane + o);
+                gx[0] = a.x; gx[1] = a.y; gx[2] = a.z; gx[3] = a.w;
+                gy[0] = c.x; gy[1] = c.y; gy[2] = c.z; gy[3] = c.w;
+            } else {
+#pragma unroll
+                for (int v = 0; v < VEC; ++v) { gx[v] = gN[o + v]; gy[v] = gN[cplane + o + v]; }
+            }
+        }
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            const float cx = fminf(fmaxf((float)(w0 + v) + gx[v], 0.f), (float)(Wc - 1)), cy = fminf(fmaxf((float)h + gy[v], 0.f), (float)(Hc - 1));
+            const int xn = (int)rintf(cx), yn = (int)rintf(cy);
+            r[v] = src[yn * W + (flip ? x0 + Wc - 1 - xn : x0 + xn)];
+        }
+        float* q = yN + o;
+        if (VEC == 4) {
+            *reinterpret_cast<float4*>(q) = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) q[v] = r[v];
         }
     }
 }
@@ -339,6 +391,26 @@ NEMAR_API int nemar_crop_flip_deform_normalize(const float* pool, const int* par
         hipLaunchKernelGGL((crop_flip_deform_normalize_kernel<1>), grid, block, 0, (hipStream_t)stream, pool, params, g, y, M, C, H, W, Hc, Wc,
                            scale);
     NEMAR_CHECK_LAUNCH("crop_flip_deform_normalize");
+    return NEMAR_OK;
+}
+
+NEMAR_API int nemar_crop_flip_deform_labels(const float* pool, const int* params, const float* g, float* y, int M, int B, int H, int W,
+                                            int Hc, int Wc, void* stream) {
+    NEMAR_CLEAR_HIP_ERROR();
+    NEMAR_REQUIRE(pool && params && y, "crop_flip_deform_labels: null pointer");
+    NEMAR_REQUIRE(M > 0 && B > 0 && B <= 65535 && Hc > 0 && Wc > 0 && Hc <= H && Wc <= W && (long long)H * W < (1ll << 31),
+                  "crop_flip_deform_labels: bad arguments");
+    NEMAR_REQUIRE((((uintptr_t)params) & 15) == 0, "crop_flip_deform_labels: params must be 16-byte aligned");
+    NEMAR_REQUIRE(((((uintptr_t)pool) | ((uintptr_t)g) | ((uintptr_t)y)) & 3) == 0, "crop_flip_deform_labels: pool, g and y must be 4-byte aligned");
+    const bool vec = (Wc & 3) == 0 && aligned16(g, y);
+    const long long items = (long long)Hc * (vec ? Wc / 4 : Wc);
+    const dim3 grid(reg_blocks(B, items), B), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (g && vec) hipLaunchKernelGGL((crop_flip_deform_labels_kernel<4, true>), grid, block, 0, st, pool, params, g, y, M, H, W, Hc, Wc);
+    else if (g) hipLaunchKernelGGL((crop_flip_deform_labels_kernel<1, true>), grid, block, 0, st, pool, params, g, y, M, H, W, Hc, Wc);
+    else if (vec) hipLaunchKernelGGL((crop_flip_deform_labels_kernel<4, false>), grid, block, 0, st, pool, params, g, y, M, H, W, Hc, Wc);
+    else hipLaunchKernelGGL((crop_flip_deform_labels_kernel<1, false>), grid, block, 0, st, pool, params, g, y, M, H, W, Hc, Wc);
+    NEMAR_CHECK_LAUNCH("crop_flip_deform_labels");
     return NEMAR_OK;
 }
 

@@ -18,19 +18,13 @@
 // none inside a segment, a few across a boundary — add for themselves.  tools/microbench_score.py times this against per-lane adds
 // (nemar_tune(45, 1), measurement build) on blocky, single-class and per-pixel-random maps: tools/profiles/label_overlap.txt.
 #include "common.h"
+#include "label_class.h"
 #include "pred_launch.h"
 #include "wave_count.h"
 
 namespace {
 
-constexpr int MAX_CLASSES = 1024;          // 3 * 1024 counters = 12 KiB of LDS beside the 9.3 KiB field patch
-
-// class of a label value: k iff v == (float)k for an integer 0 <= k < K; anything else (negative, >= K, fractional, NaN, Inf) is -1
-__device__ __forceinline__ int class_of(float v, int K) {
-    if (!(v >= 0.f && v < (float)K)) return -1;
-    const int k = (int)v;
-    return (float)k == v ? k : -1;
-}
+// (MAX_CLASSES, class_of: label_class.h — 3 * 1024 counters = 12 KiB of LDS beside the 9.3 KiB field patch)
 
 // KCAP: the histogram's capacity in classes (K <= KCAP) — 256 (3 KiB + the 9.3 KiB patch: eight workgroups fit a CU's LDS) or 1024
 // (21.3 KiB: seven)

@@ -24,7 +24,16 @@ its field g [B,2,Hc,Wc] — pixels, channel 0 = x, A'(q) = A_crop(q + g(q)) — 
 crop centre + cubic B-spline lattice) and modality A is cropped, flipped AND deformed by one launch (nemar_crop_flip_deform_normalize,
 border-clamped bilinear); B takes the plain launch.  The batch then carries 'gt_field', which the model's registration-error meter reads
 (util/visualizer.RegistrationMeter).  `--synthetic_pairs mapped` makes the synthetic pool registrable: A is a band-limited random texture,
-B a fixed per-channel non-linear remap of it (the default `independent` pools share nothing)."""
+B a fixed per-channel non-linear remap of it (the default `independent` pools share nothing).
+
+`--labels K` (default 0: off, every batch is what it is without the option, key for key) adds label maps for the soft-Dice term
+(`--lambda_dice`): a label pool [M,1,H,W] of float class ids 0 .. K-1 per modality — `labels_A.npy` / `labels_B.npy` ([M,H,W] or
+[M,1,H,W], the images' size) beside A.npy / B.npy, or for `--dataroot synthetic --synthetic_pairs mapped` the K-level quantisation of the
+channel mean of pool A, shared by both modalities (the pairs are aligned).  The label pools follow the images' resize by NEAREST
+interpolation, once, at load; a batch carries 'labels_A' and 'labels_B' [B,1,Hc,Wc] from the images' own crop window and flip
+(nemar_crop_flip_deform_labels: nearest sampling, ids copied), and under --misalign labels_A is deformed by the batch's gt_field, as image A
+is.  No random stream moves."""
+import argparse
 import ctypes
 import math
 import os
@@ -50,6 +59,9 @@ class GpuPairsDataset(BaseDataset):
         parser.add_argument('--misalign_grid', type=int, default=6, help='control points per side of the elastic lattice (>= 4)')
         parser.add_argument('--synthetic_pairs', type=str, default='independent', choices=('independent', 'mapped'),
                             help='synthetic pool: two independent noise pools, or a band-limited texture and a non-linear remap of it')
+        # (read with getattr(opt, 'labels', 0): a command line without it parses to the options it always parsed to)
+        parser.add_argument('--labels', type=int, default=argparse.SUPPRESS,
+                            help='K >= 2: serve label maps labels_A / labels_B with K classes (labels_A.npy / labels_B.npy, or the quantised synthetic mapped pool); 0: none')
         return parser
 
     def __init__(self, opt):
@@ -88,8 +100,15 @@ class GpuPairsDataset(BaseDataset):
             self.pool_A, self.paths_A = self._load(os.path.join(self.root, 'A.npy'))
             self.pool_B, self.paths_B = self._load(os.path.join(self.root, 'B.npy'))
             assert self.pool_A.shape == self.pool_B.shape, "aligned pairs: A.npy and B.npy must have the same shape"
+        self.num_labels = int(getattr(opt, 'labels', 0) or 0)
+        self.labels_A = self.labels_B = None
+        if self.num_labels:
+            self.labels_A, self.labels_B = self._label_pools()
         self.pool_A, self.pool_B = self._resize(self.pool_A), self._resize(self.pool_B)
         self.M, _, self.H, self.W = self.pool_A.shape
+        if self.num_labels:
+            self.labels_A, self.labels_B = self._resize(self.labels_A, nearest=True), self._resize(self.labels_B, nearest=True)
+            assert self.labels_A.shape == (self.M, 1, self.H, self.W) and self.labels_B.shape == (self.M, 1, self.H, self.W)
         # what a batch looks like: a square crop, or the whole image
         self.out_hw = (opt.crop_size, opt.crop_size) if 'crop' in self.pre else (self.H, self.W)
         assert self.H >= self.out_hw[0] and self.W >= self.out_hw[1], "images smaller than the crop"
@@ -112,6 +131,29 @@ class GpuPairsDataset(BaseDataset):
         maps = (lambda v: 1.0 - v * v, lambda v: 0.5 - 0.5 * torch.cos(math.pi * v), lambda v: v.sqrt())
         return torch.stack([maps[ch % 3](a[:, ch]) for ch in range(a.shape[1])], dim=1).clamp_(0.0, 1.0).contiguous()
 
+    def _label_pools(self):
+        """the two label pools [M,1,H,W] float32 at the size of the image pools as loaded (before _resize)"""
+        K = self.num_labels
+        if K < 2:
+            raise ValueError('--labels %d: at least 2 classes (0 turns label maps off)' % K)
+        if self.root == 'synthetic':
+            if getattr(self.opt, 'synthetic_pairs', 'independent') != 'mapped':
+                raise ValueError('--labels with --dataroot synthetic needs --synthetic_pairs mapped: independent noise pools have no structure to label')
+            lab = (self.pool_A.mean(dim=1, keepdim=True) * K).floor().clamp_(0, K - 1).contiguous()
+            return lab, lab
+        pools = []
+        for name in ('labels_A.npy', 'labels_B.npy'):
+            path = os.path.join(self.root, name)
+            if not os.path.exists(path):
+                raise FileNotFoundError('--labels %d: %s not found (label maps [M,H,W] or [M,1,H,W] of the size of the images in A.npy / B.npy)' % (K, path))
+            a = np.load(path)
+            if a.ndim == 3:
+                a = a[:, None]
+            if a.ndim != 4 or a.shape[1] != 1 or (a.shape[0],) + a.shape[2:] != (self.pool_A.shape[0],) + tuple(self.pool_A.shape[2:]):
+                raise ValueError('%s: shape %s, expected [M,H,W] or [M,1,H,W] with M, H, W = %s' % (path, a.shape, (self.pool_A.shape[0],) + tuple(self.pool_A.shape[2:])))
+            pools.append(torch.from_numpy(np.ascontiguousarray(a)).to(self.device, torch.float32).contiguous())
+        return pools
+
     def _draw_misalign(self, n):
         """[n, 6 + 2 L L] float32 parameter rows of nemar_deform_field: a11 a12 tx a21 a22 ty (scale * rotation about the crop centre +
         translation; the identity without `affine`), then the [2, L, L] lattice (L = 0 without `elastic`)"""
@@ -130,8 +172,9 @@ class GpuPairsDataset(BaseDataset):
                 rows[b, 6 + k] = rng.uniform(-max_px, max_px)
         return rows
 
-    def _resize(self, pool):
-        """the image-only part of get_transform: resize / scale_width / make_power_2 (reference data/base_dataset.py:86-99), once"""
+    def _resize(self, pool, nearest=False):
+        """the image-only part of get_transform: resize / scale_width / make_power_2 (reference data/base_dataset.py:86-99), once
+        (nearest: a label pool — ids are picked, not blended)"""
         opt, (h, w) = self.opt, pool.shape[2:]
         if 'resize' in self.pre:
             nh, nw = opt.load_size, opt.load_size
@@ -141,6 +184,8 @@ class GpuPairsDataset(BaseDataset):
             nh, nw = int(round(h / 4) * 4), int(round(w / 4) * 4)
         else:
             nh, nw = h, w
+        if nearest:
+            return pool if (nh, nw) == (h, w) else torch.nn.functional.interpolate(pool, size=(nh, nw), mode='nearest').contiguous()
         return self.resize_to(pool, nh, nw)
 
     @staticmethod
@@ -205,6 +250,9 @@ class GpuPairsDataset(BaseDataset):
         out['B_paths'] = [self.paths_B[i % self.M] for i in indices]
         if gt is not None:
             out['gt_field'] = gt
+        if self.num_labels:
+            out['labels_A'] = ops.crop_flip_deform_labels(self.labels_A, d_params, gt, hc, wc)
+            out['labels_B'] = ops.crop_flip_deform_labels(self.labels_B, d_params, None, hc, wc)
         self._last_params = params
         return out
 

@@ -103,6 +103,17 @@ class NEMARModel(BaseModel):
                                      'the known misalignment (needs --misalign affine|elastic|both); default 0.0: switched off')
             parser.add_argument('--epe_eps', type=float, default=argparse.SUPPRESS,
                                 help='Charbonnier epsilon of the supervised registration term in pixels, > 0 (default 0.01)')
+            # (MI355X build) train against label overlap: the soft Dice of the batch's label maps (--labels K), labels_A warped by the
+            # prediction the warp reads against labels_B (ops.dice_loss).  Read like --lambda_fold
+            parser.add_argument('--lambda_dice', type=float, default=argparse.SUPPRESS,
+                                help='weight of the label-overlap term, mean 1 - soft Dice over samples and classes (needs batches with '
+                                     'labels_A / labels_B: --labels K); default 0.0: switched off')
+            parser.add_argument('--dice_eps', type=float, default=argparse.SUPPRESS,
+                                help='smoothing constant of the soft Dice in pixels, > 0 (default 1.0)')
+            parser.add_argument('--dice_classes', type=int, default=argparse.SUPPRESS,
+                                help='number of classes of the label-overlap term (default: --labels)')
+            parser.add_argument('--dice_background', action='store_true', default=argparse.SUPPRESS,
+                                help='average the label-overlap term over class 0 too (default: the background is left out)')
             parser.add_argument('--enable_tbvis', action='store_true',
                                 help='Enable tensorboard visualizer (default : False)')
             parser.add_argument('--multi_resolution', type=int, default=1,
@@ -135,6 +146,15 @@ class NEMARModel(BaseModel):
         self._epe_on = bool(self.isTrain and self._lambda_epe != 0.0)
         if self._epe_on and not self._epe_eps > 0.0:
             raise ValueError('--epe_eps %g: the Charbonnier epsilon of --lambda_epe must be positive' % self._epe_eps)
+        # the label-overlap term: one more loss of the training step on batches that carry label maps, any STN
+        self._lambda_dice, self._dice_eps = float(getattr(opt, 'lambda_dice', 0.0)), float(getattr(opt, 'dice_eps', 1.0))
+        self._dice_classes = int(getattr(opt, 'dice_classes', 0) or getattr(opt, 'labels', 0) or 0)
+        self._dice_background = bool(getattr(opt, 'dice_background', False))
+        self._dice_on = bool(self.isTrain and self._lambda_dice != 0.0)
+        if self._dice_on and self._dice_classes < 2:
+            raise ValueError('--lambda_dice %g needs at least 2 classes: --dice_classes K, or --labels K (got %d)' % (self._lambda_dice, self._dice_classes))
+        if self._dice_on and not (self._dice_eps > 0.0 and self._dice_eps < float('inf')):
+            raise ValueError('--dice_eps %g: the smoothing constant of --lambda_dice must be positive and finite' % self._dice_eps)
         self.setup_visualizers()
         self.tb_visualizer = None
         # T's two applications and D's 3 + 2 applications per step run as single batches: the same graph with half the launches.  (With
@@ -162,6 +182,8 @@ class NEMARModel(BaseModel):
                 self._lam_fold = torch.full((), self._lambda_fold, dtype=torch.float32, device=self.device)
             if self._epe_on:
                 self._lam_epe = torch.full((), self._lambda_epe, dtype=torch.float32, device=self.device)
+            if self._dice_on:
+                self._lam_dice = torch.full((), self._lambda_dice, dtype=torch.float32, device=self.device)
 
     loss_L1_TR = _loss_property('L1_TR')
     loss_GAN_TR = _loss_property('GAN_TR')
@@ -170,6 +192,7 @@ class NEMARModel(BaseModel):
     loss_smoothness = _loss_property('smoothness')
     loss_fold = _loss_property('fold')
     loss_EPE = _loss_property('EPE')
+    loss_Dice = _loss_property('Dice')
     loss_LNCC_TR = _loss_property('LNCC_TR')
     loss_LNCC_RT = _loss_property('LNCC_RT')
     loss_D_fake_TR = _loss_property('D_fake_TR')
@@ -183,6 +206,9 @@ class NEMARModel(BaseModel):
             self.loss_names.insert(self.loss_names.index('smoothness') + 1, 'fold')
         if self._epe_on:
             self.loss_names.insert(self.loss_names.index('fold' if self._fold_on else 'smoothness') + 1, 'EPE')
+        if self._dice_on:
+            after = 'EPE' if self._epe_on else ('fold' if self._fold_on else 'smoothness')
+            self.loss_names.insert(self.loss_names.index(after) + 1, 'Dice')
         if self._lncc_on:
             at = self.loss_names.index('smoothness')
             self.loss_names[at:at] = ['LNCC_TR', 'LNCC_RT']
@@ -237,6 +263,12 @@ class NEMARModel(BaseModel):
         if gt is not None and not AtoB:
             raise ValueError('gt_field describes the deformation of modality A: the registration error is defined for --direction AtoB')
         self.gt_field = None if gt is None else gt.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
+        # label maps (data/gpupairs_dataset.py --labels): float class ids [N,1,H,W] of the two modalities, for the label-overlap term
+        la, lb = input.get('labels_A'), input.get('labels_B')
+        if (la is not None or lb is not None) and not AtoB:
+            raise ValueError('labels_A / labels_B: the label-overlap term warps the labels of modality A: it is defined for --direction AtoB')
+        self.labels_A = None if la is None else la.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
+        self.labels_B = None if lb is None else lb.to(self.device, dtype=torch.float32, non_blocking=True).contiguous()
         self._resized = {}
 
     def registration_error(self):
@@ -415,16 +447,30 @@ class NEMARModel(BaseModel):
     # ---- forward -------------------------------------------------------------------------------------------
     def _fork_prediction(self, n_warps):
         """netR's prediction for the set_input pair as handles (netR.fork_field): one per warp, the regulariser's, and — None where the
-        term is off — the fold term's and the EPE term's"""
+        term is off — the fold term's, the EPE term's and the label-overlap term's"""
         kw = {}
         if self._fold_on:
             kw['fold'] = True
-        if self._epe_on:
-            kw['extra'] = 1
+        extra = int(self._epe_on) + int(self._dice_on)
+        if extra:
+            kw['extra'] = extra
         out = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), n_warps, **kw)
-        return out[0], out[1], (out[2] if self._fold_on else None), (out[-1][0] if self._epe_on else None)
+        more = list(out[-1]) if extra else []
+        return (out[0], out[1], (out[2] if self._fold_on else None), (more.pop(0) if self._epe_on else None),
+                (more.pop(0) if self._dice_on else None))
 
-    def _further_stn_terms(self, f_fold, f_epe):
+    def _dice_labels(self, what):
+        """the batch's two label maps, checked"""
+        la, lb = getattr(self, 'labels_A', None), getattr(self, 'labels_B', None)
+        if la is None or lb is None:
+            raise RuntimeError('%s--lambda_dice %g: the current batch carries no labels_A / labels_B to train against (--labels K of the '
+                               'gpupairs dataset)' % (what, self._lambda_dice))
+        want = (self.real_A.size(0), 1, self.real_A.size(2), self.real_A.size(3))
+        if tuple(la.shape) != want or tuple(lb.shape) != want:
+            raise ValueError('--lambda_dice: labels_A %s / labels_B %s are not the size of the prediction, %s' % (tuple(la.shape), tuple(lb.shape), want))
+        return la, lb
+
+    def _further_stn_terms(self, f_fold, f_epe, f_dice=None):
         if self._fold_on:
             self.stn_fold_term = self.netR.fold_term(f_fold, self._fold_margin)
         if self._epe_on:
@@ -436,17 +482,20 @@ class NEMARModel(BaseModel):
             if tuple(gt.shape) != want:
                 raise ValueError('--lambda_epe: gt_field %s is not the size of the prediction, %s' % (tuple(gt.shape), want))
             self.stn_epe_term = self.netR.epe_term(f_epe, gt, self._epe_eps)
+        if self._dice_on:
+            la, lb = self._dice_labels('')
+            self.stn_dice_term = self.netR.dice_term(f_dice, la, lb, self._dice_classes, self._dice_eps, self._dice_background)
 
     def forward(self):
         if not self._batched:
             # the reference's own order (models/nemar_model.py:161-176)
             self.fake_B = self.netT(self.real_A)
-            if self._fold_on or self._epe_on:
+            if self._fold_on or self._epe_on or self._dice_on:
                 # netR.forward() piece by piece, with one more handle of the field for each further term
-                (f_warp,), f_reg, f_fold, f_epe = self._fork_prediction(1)
+                (f_warp,), f_reg, f_fold, f_epe, f_dice = self._fork_prediction(1)
                 warped = self.netR.warp(f_warp, [self.real_A, self.fake_B])
                 reg_term = self.netR.regularization(f_reg, warped[0])
-                self._further_stn_terms(f_fold, f_epe)
+                self._further_stn_terms(f_fold, f_epe, f_dice)
             else:
                 warped, reg_term = self.netR(self.real_A, self.real_B, apply_on=[self.real_A, self.fake_B])
             self.stn_reg_term = reg_term
@@ -461,7 +510,7 @@ class NEMARModel(BaseModel):
             n = self.real_A.size(0)
             # (the field has three consumers — two warps and the regulariser —, the batch of T two sources and two slices: the library's own
             # nodes for fan-out, concatenation and slicing, ops.fork / cat_batch / split_batch, instead of autograd's ATen kernels)
-            (f_a, f_b), f_reg, f_fold, f_epe = self._fork_prediction(2)
+            (f_a, f_b), f_reg, f_fold, f_epe, f_dice = self._fork_prediction(2)
             self.registered_real_A = self.netR.warp(f_a, [self.real_A])[0]
             # (only the second half is differentiated: the stem's data gradient runs on it alone)
             with ops.norm_segments(2):
@@ -469,7 +518,7 @@ class NEMARModel(BaseModel):
             self.fake_B, self.fake_TR_B = ops.split_batch(both, 2)
             self.fake_RT_B = self.netR.warp(f_b, [self.fake_B])[0]
             self.stn_reg_term = self.netR.regularization(f_reg, self.registered_real_A)
-            self._further_stn_terms(f_fold, f_epe)
+            self._further_stn_terms(f_fold, f_epe, f_dice)
         self._resized = {}
         if self.tb_visualizer is not None:
             # the reference runs netR a second time here (get_grid, :172-173); the field of the pass above is the same tensor
@@ -578,6 +627,11 @@ class NEMARModel(BaseModel):
             roots.append(self.stn_epe_term)         # likewise
             grads.append(self._lam_epe)
             total.append((self.stn_epe_term, self._lambda_epe))
+        if self._dice_on:
+            self.loss_Dice = _LazyLoss([(self.stn_dice_term, self._lambda_dice)])
+            roots.append(self.stn_dice_term)        # likewise
+            grads.append(self._lam_dice)
+            total.append((self.stn_dice_term, self._lambda_dice))
         if self._lncc_on:
             # two more roots, against real_B as the L1 terms are; the weight is the kernel's factor
             lncc = [ops.local_ncc(h, self.real_B.detach(), self._lncc_win, factor=self._lambda_lncc) for h in (tr_cc, rt_cc)]
@@ -608,6 +662,12 @@ class NEMARModel(BaseModel):
                                    'affine|elastic|both)' % self._lambda_epe)
             self._static_gt = self.gt_field.clone()
             self.gt_field = self._static_gt
+        # ... and the label-overlap term the batch's two label maps
+        self._static_labels = None
+        if self._dice_on:
+            la, lb = self._dice_labels('enable_step_graph: ')
+            self._static_labels = (la.clone(), lb.clone())
+            self.labels_A, self.labels_B = self._static_labels
         opts =[self.optimizer_D, self.optimizer_R, self.optimizer_T]
         # The warm-up steps must not train: they run with lr = 0 (Adam leaves every parameter bit-unchanged: p - 0 * x) and the
         # moments, step counts and the dropout step counter are put back afterwards — the first replay is then step 1 of the same
@@ -661,6 +721,10 @@ class NEMARModel(BaseModel):
     def _replay_step(self):
         static_gt = getattr(self, '_static_gt', None)
         gt_fits = static_gt is None or (getattr(self, 'gt_field', None) is not None and self.gt_field.shape == static_gt.shape)
+        static_labels = getattr(self, '_static_labels', None)
+        if static_labels is not None:
+            la, lb = getattr(self, 'labels_A', None), getattr(self, 'labels_B', None)
+            gt_fits = gt_fits and la is not None and lb is not None and la.shape == static_labels[0].shape and lb.shape == static_labels[1].shape
         if self.real_A.shape != self._static_A.shape or self.real_B.shape != self._static_B.shape or not gt_fits:
             # a batch of another shape (the ragged last batch of an epoch): the captured launches do not describe it — run this step
             # eagerly, in the same device-parameter mode (bit-identical arithmetic), and keep the graph for the next full batch
@@ -673,6 +737,10 @@ class NEMARModel(BaseModel):
         if static_gt is not None and self.gt_field is not static_gt:
             static_gt.copy_(self.gt_field)
             self.gt_field = static_gt
+        if static_labels is not None and self.labels_A is not static_labels[0]:
+            static_labels[0].copy_(self.labels_A)
+            static_labels[1].copy_(self.labels_B)
+            self.labels_A, self.labels_B = static_labels
         ops.begin_step()
         for o in (self.optimizer_D, self.optimizer_R, self.optimizer_T):
             o.prepare_step(o.step_count + 1)

@@ -137,7 +137,7 @@ class AffineSTN(nn.Module):
 
     def fork_field(self, field, n_warps, extra=0):
         """-> ([one theta handle per warp() call], the handle for regularization()) — ops.fork, as UnetSTN.fork_field; with
-        extra = k > 0 a last element: a list of k more handles, one per further consumer (epe_term())"""
+        extra = k > 0 a last element: a list of k more handles, one per further consumer (epe_term(), dice_term())"""
         hs = ops.fork(field, n_warps + 1 + int(extra))
         out = list(hs[:n_warps]), hs[n_warps]
         return (*out, list(hs[n_warps + 1:])) if extra else out
@@ -146,6 +146,11 @@ class AffineSTN(nn.Module):
         """mean over all pixels of sqrt(|r|^2 + eps^2), r the residual registration_error measures against the ground-truth field
         gt_field [N,2,h,w] in pixels, for the sampling positions of affine_grid(theta) at the field's size (ops.epe_loss)"""
         return ops.epe_loss(field, ops.GRID_AFFINE, gt_field, eps, 1.0)
+
+    def dice_term(self, field, labels_moving, labels_fixed, num_classes, eps=1.0, background=False):
+        """mean over samples and classes of 1 - soft Dice of labels_moving warped bilinearly by affine_grid(theta) at the label maps'
+        size against labels_fixed, both [N,1,h,w] (or [N,h,w]) float class ids (ops.dice_loss)"""
+        return ops.dice_loss(field, ops.GRID_AFFINE, labels_moving, labels_fixed, num_classes, eps, background, 1.0)
 
     def regularization(self, field, warped_first=None):
         return self._calculate_regularization_term(field)

@@ -224,7 +224,7 @@ class UnetSTN(nn.Module):
         """-> ([one field per warp() call], the field for regularization()): handles of the same tensors (ops.fork), so that the
         consumers' gradients are added by the library's kernel instead of autograd's accumulation.  With fold=True a third element:
         one more handle of the field the warp reads, for fold_term().  With extra = k > 0 a last element: a list of k more such
-        handles, one per further consumer of the field the warp reads (epe_term())."""
+        handles, one per further consumer of the field the warp reads (epe_term(), dice_term())."""
         d, d_up = field
         more = (1 if fold else 0) + int(extra)
         if d_up is d:
@@ -253,6 +253,11 @@ class UnetSTN(nn.Module):
         gt_field [N,2,oh,ow] in pixels (ops.epe_loss), on the field the warp reads — past the integration and the low-resolution
         resize, where fold_term() acts."""
         return ops.epe_loss(field[1], ops.GRID_UNET, gt_field, eps, 1.0)
+
+    def dice_term(self, field, labels_moving, labels_fixed, num_classes, eps=1.0, background=False):
+        """mean over samples and classes of 1 - soft Dice of labels_moving warped bilinearly by the field the warp reads against
+        labels_fixed, both [N,1,oh,ow] (or [N,oh,ow]) float class ids (ops.dice_loss) — where epe_term() acts."""
+        return ops.dice_loss(field[1], ops.GRID_UNET, labels_moving, labels_fixed, num_classes, eps, background, 1.0)
 
     def regularization(self, field, warped_first):
         return self._calculate_regularization_term(field[0], warped_first)

@@ -2022,6 +2022,23 @@ def crop_flip_deform_normalize(pool, crop_params, g, Hc, Wc, scale=1.0):
     return y
 
 
+def crop_flip_deform_labels(pool, crop_params, g, Hc, Wc):
+    """The label twin of crop_flip_deform_normalize: pool [M,1,H,W] (or [M,H,W]) float class ids cropped and flipped by crop_params
+    [B,4] int32, each output pixel q read at q + g(q) (g [B,2,Hc,Wc] in pixels, or None: the plain crop / flip) clamped to the crop
+    window, by nearest sampling (round half to even) — class ids are copied, never blended or normalised -> [B,1,Hc,Wc]."""
+    pool = _c(pool)
+    if pool.dim() == 3:
+        pool = pool[:, None]
+    M, C, H, W = pool.shape
+    B = crop_params.shape[0]
+    g = None if g is None else _c(g.detach())
+    if C != 1 or crop_params.dtype != torch.int32 or tuple(crop_params.shape) != (B, 4) or (g is not None and tuple(g.shape) != (B, 2, Hc, Wc)):
+        raise ValueError("crop_flip_deform_labels: pool [M,1,H,W], crop_params [B,4] int32 and g [B,2,Hc,Wc] (or None) expected")
+    y = torch.empty((B, 1, Hc, Wc), dtype=torch.float32, device=pool.device)
+    L.crop_flip_deform_labels(_p(pool), _p(crop_params.contiguous()), _p(g), _p(y), M, B, H, W, Hc, Wc, _stream())
+    return y
+
+
 REG_COLUMNS = ('valid_count', 'sum_r', 'max_r', 'sum_g', 'fold_count', 'interior_count')
 
 
@@ -2151,6 +2168,82 @@ def epe_loss(pred, grid_mode, gt_field, eps=0.01, factor=1.0):
     if not float(eps) > 0.0:
         raise ValueError("epe_loss: eps %r must be positive (at eps = 0 the gradient of a zero residual is NaN)" % (eps,))
     return _EpeLoss.apply(pred, int(grid_mode), gt_field.detach(), float(eps), float(factor))
+
+
+class _DiceLoss(Function):
+    @staticmethod
+    def forward(ctx, pred, mode, lm, lf, K, k0, eps, factor):
+        pred = _c(pred)
+        N, H, W = lf.shape
+        loss = torch.empty((1,), dtype=torch.float32, device=lf.device)
+        sums = torch.empty((N, K, 3), dtype=torch.int64, device=lf.device)
+        coef = torch.empty((N, K, 2), dtype=torch.float32, device=lf.device)
+        L.dice_loss_fwd(_p(pred), mode, _p(lm), _p(lf), K, k0, eps, factor, _p(loss), 0, _p(sums), _p(coef), N, H, W, _stream())
+        ctx.save_for_backward(pred, lm, lf, coef)
+        ctx.cfg = (mode, K)
+        return loss.reshape(())
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        pred, lm, lf, coef = ctx.saved_tensors
+        mode, K = ctx.cfg
+        N, H, W = lf.shape
+        gpred = torch.empty_like(pred)
+        wsb = Q.dice_loss_workspace(N, H, W)
+        ws = _workspace(wsb, lf.device)
+        L.dice_loss_bwd(_p(pred), mode, _p(lm), _p(lf), _p(coef), K, _p(_c(gout)), _p(gpred), 0, _p(ws), wsb, N, H, W, _stream())
+        return gpred, None, None, None, None, None, None, None
+
+
+DICE_COLUMNS = ('inter', 'moving', 'fixed')
+DICE_FIX_BITS = 30
+
+
+def _dice_args(what, pred, grid_mode, labels_moving, labels_fixed, num_classes):
+    if grid_mode not in (GRID_UNET, GRID_AFFINE):
+        raise ValueError("%s: grid mode %r (GRID_UNET or GRID_AFFINE)" % (what, grid_mode))
+    N = int(pred.shape[0])
+    lm, lf = _label_planes(what, labels_moving.detach(), N), _label_planes(what, labels_fixed.detach(), N)
+    if lm.shape != lf.shape:
+        raise ValueError("%s: label maps %s and %s: the loss is taken at the prediction's own size" % (what, tuple(lm.shape), tuple(lf.shape)))
+    _, H, W = lf.shape
+    want = (N, 2, H, W) if grid_mode == GRID_UNET else (N, 6)
+    if tuple(pred.shape) != want:
+        raise ValueError("%s: prediction %s, expected %s for label maps %s" % (what, tuple(pred.shape), want, tuple(lf.shape)))
+    K = int(num_classes)
+    if not 1 <= K <= 1024:
+        raise ValueError("%s: %d classes (1 .. 1024)" % (what, K))
+    return lm, lf, K
+
+
+def dice_sums(pred, grid_mode, labels_moving, labels_fixed, num_classes):
+    """The soft overlap sums of dice_loss (nemar_dice_sums): float64 [N,K,3] in pixels, columns DICE_COLUMNS per class k — I = sum of
+    p_k f_k, M = sum of p_k, F = sum of f_k, p_k the bilinear (zeros-padded) warp of the moving map's class-k indicator by the
+    prediction, f_k the fixed map's.  The library's integers (30 fractional bits for I and M) divided once: bitwise repeatable.  No
+    autograd, no sync."""
+    lm, lf, K = _dice_args("dice_sums", pred, grid_mode, labels_moving, labels_fixed, num_classes)
+    N, H, W = lf.shape
+    raw = torch.empty((N, K, 3), dtype=torch.int64, device=lf.device)
+    L.dice_sums(_p(_c(pred.detach())), int(grid_mode), _p(lm), _p(lf), _p(raw), N, K, H, W, _stream())
+    out = raw.to(torch.float64)
+    out[..., :2] *= 2.0 ** -DICE_FIX_BITS
+    return out
+
+
+def dice_loss(pred, grid_mode, labels_moving, labels_fixed, num_classes, eps=1.0, background=False, factor=1.0):
+    """factor * mean over samples and classes of 1 - (2 I + eps) / (M + F + eps), the soft Dice of labels_moving [N,H,W] (or [N,1,H,W];
+    float class ids, label_overlap's rule) warped bilinearly with zeros padding by the prediction pred (GRID_UNET: offsets [N,2,H,W];
+    GRID_AFFINE: dtheta [N,6]) against labels_fixed at the same size (nemar_dice_loss_fwd / _bwd; dice_sums for I, M, F).  eps > 0 in
+    pixels; the background class 0 is left out of the mean unless background=True.  A 0-dim device tensor with a gradient towards pred
+    only; a pixel whose sampling position is not finite is left out and gets gradient 0.  No sync."""
+    lm, lf, K = _dice_args("dice_loss", pred, grid_mode, labels_moving, labels_fixed, num_classes)
+    k0 = 0 if background else 1
+    if K <= k0:
+        raise ValueError("dice_loss: %d classes with the background left out: nothing to average (num_classes >= 2, or background=True)" % K)
+    if not (float(eps) > 0.0 and float(eps) < float('inf')):
+        raise ValueError("dice_loss: eps %r must be positive and finite" % (eps,))
+    return _DiceLoss.apply(pred, int(grid_mode), lm, lf, K, k0, float(eps), float(factor))
 
 
 class _LocalNCC(Function):
