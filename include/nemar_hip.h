@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 615 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 616 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -215,6 +215,44 @@ int nemar_local_ncc_fwd(const float* x, const float* y, int win, float eps, floa
                         void* workspace, size_t ws_bytes, int N, int C, int H, int W, void* stream);
 int nemar_local_ncc_bwd(const float* x, const float* y, int win, float eps, const float* gscale, float factor, float* gx, float* gy,
                         int accumulate, int N, int C, int H, int W, void* stream);
+
+/* MIND (csrc/mind.hip; not a call site of the reference, whose image terms compare two images of one modality): the modality-independent
+ * neighbourhood descriptor (Heinrich et al. 2012) as a differentiable loss between two modalities.  x [N,Cx,H,W], y [N,Cy,H,W], planar;
+ * Cx and Cy may differ.  Each image enters through its channel mean, as in nemar_joint_histogram: g(q) = (1/C) sum_c img[n,c,q].
+ * patch: 3 or 5, radius p = patch / 2.  dil: 1 or 2.  eps > 0.  The four search offsets s = (0,-dil), (0,+dil), (-dil,0), (+dil,0) as
+ * (dy, dx), in that order.
+ *   E_s(q) = ( g(q) - g(clamp(q + s)) )^2           q in the image; clamp = each coordinate to [0,H-1] / [0,W-1]
+ *   D_s(u) = (1 / n(u)) sum_{q in Omega(u)} E_s(q)   Omega(u) = the in-image part of the patch x patch square at u, n(u) = |Omega(u)|
+ *                                                    (no zero padding)
+ *   V(u)   = (1/4) sum_s D_s(u)
+ *   m_s(u) = exp( -D_s(u) / (V(u) + eps) )
+ *   dm(u)  = (1/4) sum_s ( m_s^x(u) - m_s^y(u) )^2
+ *   loss   = factor * (1 / (N H W)) sum_{n,u} dm(u)
+ * This is MIND without the division by max_s m_s (equivalently without the - min_s D_s): that step has a kink wherever two D_s tie, and
+ * the descriptors stay bounded without it (sum_s D_s / V = 4).  Every quantity is invariant to a constant added to x or to y, and the
+ * map is symmetric in x and y.  exp is the library's expf, not the hardware approximation.
+ * fwd: loss[0] = (accumulate ? loss[0] : 0) + loss;  dm_map [N,1,H,W] = dm, or NULL.  One record per workgroup (a 32 x 16 tile of one
+ *      sample) goes to the workspace, the records are merged in a fixed order: no atomics, bitwise repeatable.
+ * bwd: with c = factor / (4 N H W),
+ *        a_s(u) = 2 c (m_s^x - m_s^y)
+ *        b_s(u) = -a_s m_s / (V + eps) + (1 / (4 (V + eps)^2)) sum_r a_r m_r D_r
+ *        e_s(q) = sum_{u : q in Omega(u)} b_s(u) / n(u)
+ *        dL/dg(t) = sum_s [ 2 e_s(t) (g(t) - g(clamp(t + s))) - sum_{q : clamp(q + s) = t} 2 e_s(q) (g(q) - g(t)) ]
+ *        gx[n,c,t] (+)= gscale[0] * dL/dg(t) / Cx, the same value for every channel
+ *      (m, V, D those of x; the inner sum has one term in the interior, q = t - s, and up to dil + 1 on the border rows or columns that
+ *      the clamp maps onto).  gscale: device scalar, the upstream gradient.  gy [N,Cy,H,W] or NULL: the same with the roles of x and y
+ *      swapped.  One launch on 32 x 16 tiles with a halo of 2 (p + dil), a gather: no atomics, no workspace, bitwise repeatable.
+ * NEMAR_EINVAL, nothing launched: patch not 3 or 5; dil not 1 or 2; eps <= 0 (or NaN); a required pointer NULL (x, y, loss, workspace;
+ * x, y, gscale, gx) or any pointer not 4-byte aligned (all the alignment asked for; rows are read with 16-byte loads where the base is
+ * 16-byte aligned and W % 4 == 0); a non-positive N, Cx, Cy, H or W; N > 65535; H*W >= 2^31; dm_map, gx or gy overlapping x or y, gy
+ * overlapping gx; ws_bytes < nemar_mind_loss_workspace() (which is 0 for arguments the calls refuse).  Non-finite input: NEMAR_OK, NaN
+ * or Inf in the outputs that hear from it (within p + dil of it forward, 2 (p + dil) backward), no access outside the buffers (no index
+ * depends on the data). */
+size_t nemar_mind_loss_workspace(int N, int H, int W, int patch, int dil);
+int nemar_mind_loss_fwd(const float* x, int Cx, const float* y, int Cy, int patch, int dil, float eps, float factor, float* loss,
+                        int accumulate, float* dm_map, void* workspace, size_t ws_bytes, int N, int H, int W, void* stream);
+int nemar_mind_loss_bwd(const float* x, int Cx, const float* y, int Cy, int patch, int dil, float eps, const float* gscale, float factor,
+                        float* gx, float* gy, int accumulate, int N, int H, int W, void* stream);
 
 /* Scaling and squaring (csrc/integrate.hip; not in the reference, whose UNet STN warps with the network's output as it is): the network's
  * output as a stationary velocity field v, the warp reads exp(v).  One squaring step on a displacement field u [N,2,H,W], planar, in the

@@ -55,6 +55,9 @@ SIGNATURES = {
     "nemar_local_ncc_workspace": (_sz, [_i, _i, _i, _i, _i]),
     "nemar_local_ncc_fwd": (_i, [_vp, _vp, _i, _fl, _fl, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _i, _vp]),
     "nemar_local_ncc_bwd": (_i, [_vp, _vp, _i, _fl, _vp, _fl, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "nemar_mind_loss_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "nemar_mind_loss_fwd": (_i, [_vp, _i, _vp, _i, _i, _i, _fl, _fl, _vp, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "nemar_mind_loss_bwd": (_i, [_vp, _i, _vp, _i, _i, _i, _fl, _vp, _fl, _vp, _vp, _i, _i, _i, _i, _vp]),
     "nemar_svf_step_fwd": (_i, [_vp, _fl, _vp, _i, _i, _i, _vp]),
     "nemar_svf_step_bwd_workspace": (_sz, [_i, _i, _i]),
     "nemar_svf_step_bwd_zeroed_bytes": (_sz, [_i, _i, _i]),

@@ -96,6 +96,16 @@ class NEMARModel(BaseModel):
                                 help='weight of the local NCC terms, 1 - mean cc of fake_TR_B / fake_RT_B with real_B; default 0.0: switched off')
             parser.add_argument('--lncc_win', type=int, default=argparse.SUPPRESS,
                                 help='window size of the local NCC terms: odd, 3 .. 11 (default 9)')
+            # (MI355X build) train across modalities: the distance of the MIND descriptors of registered_real_A and real_B (ops.mind_loss),
+            # an image term that compares modality A with modality B directly and reaches netR alone.  Read like --lambda_fold
+            parser.add_argument('--lambda_mind', type=float, default=argparse.SUPPRESS,
+                                help='weight of the MIND term, the mean squared descriptor distance of registered_real_A and real_B; '
+                                     'default 0.0: switched off')
+            parser.add_argument('--mind_patch', type=int, default=argparse.SUPPRESS, help='patch size of the MIND term: 3 or 5 (default 3)')
+            parser.add_argument('--mind_dilation', type=int, default=argparse.SUPPRESS,
+                                help='distance of the four neighbouring patches of the MIND term: 1 or 2 (default 2)')
+            parser.add_argument('--mind_eps', type=float, default=argparse.SUPPRESS,
+                                help='constant added to the local variance of the MIND term, > 0 (default 1e-5)')
             # (MI355X build) train against known misalignment: the registration error of batches that carry a ground-truth field
             # (--misalign), as a loss on the prediction the warp reads (ops.epe_loss).  Read like --lambda_fold
             parser.add_argument('--lambda_epe', type=float, default=argparse.SUPPRESS,
@@ -141,6 +151,17 @@ class NEMARModel(BaseModel):
         self._lncc_on = bool(self.isTrain and self._lambda_lncc != 0.0)
         if self._lncc_on and not (3 <= self._lncc_win <= 11 and self._lncc_win % 2 == 1):
             raise ValueError('--lncc_win %d: the local NCC window is an odd size from 3 to 11' % self._lncc_win)
+        # the MIND term: one more image loss of the training step, registered_real_A against real_B across the modalities, any STN
+        self._lambda_mind = float(getattr(opt, 'lambda_mind', 0.0))
+        self._mind_patch, self._mind_dil = int(getattr(opt, 'mind_patch', 3)), int(getattr(opt, 'mind_dilation', 2))
+        self._mind_eps = float(getattr(opt, 'mind_eps', 1e-5))
+        self._mind_on = bool(self.isTrain and self._lambda_mind != 0.0)
+        if self._mind_on and self._mind_patch not in (3, 5):
+            raise ValueError('--mind_patch %d: the patch of the MIND term is 3 or 5' % self._mind_patch)
+        if self._mind_on and self._mind_dil not in (1, 2):
+            raise ValueError('--mind_dilation %d: the dilation of the MIND term is 1 or 2' % self._mind_dil)
+        if self._mind_on and not self._mind_eps > 0.0:
+            raise ValueError('--mind_eps %g: the constant of the MIND term must be positive' % self._mind_eps)
         # the supervised registration term: one more loss of the training step on batches that carry a gt_field, any STN
         self._lambda_epe, self._epe_eps = float(getattr(opt, 'lambda_epe', 0.0)), float(getattr(opt, 'epe_eps', 0.01))
         self._epe_on = bool(self.isTrain and self._lambda_epe != 0.0)
@@ -195,6 +216,7 @@ class NEMARModel(BaseModel):
     loss_Dice = _loss_property('Dice')
     loss_LNCC_TR = _loss_property('LNCC_TR')
     loss_LNCC_RT = _loss_property('LNCC_RT')
+    loss_MIND_R = _loss_property('MIND_R')
     loss_D_fake_TR = _loss_property('D_fake_TR')
     loss_D_fake_RT = _loss_property('D_fake_RT')
     loss_D = _loss_property('D')
@@ -212,6 +234,8 @@ class NEMARModel(BaseModel):
         if self._lncc_on:
             at = self.loss_names.index('smoothness')
             self.loss_names[at:at] = ['LNCC_TR', 'LNCC_RT']
+        if self._mind_on:
+            self.loss_names.insert(self.loss_names.index('smoothness'), 'MIND_R')      # (after the local NCC names)
         self.visual_names = ['real_A', 'real_B', 'fake_TR_B', 'fake_RT_B', 'registered_real_A', 'fake_B']
         self.model_names = ['T', 'R'] + (['D'] if self.isTrain else [])
 
@@ -486,6 +510,14 @@ class NEMARModel(BaseModel):
             la, lb = self._dice_labels('')
             self.stn_dice_term = self.netR.dice_term(f_dice, la, lb, self._dice_classes, self._dice_eps, self._dice_background)
 
+    def _registered_for_netT(self):
+        """registered_real_A as netT reads it.  With the MIND term on the image has two consumers, netT and the term: two handles
+        (ops.fork), the term's kept for backward_T_and_R; self.registered_real_A stays the tensor visuals and cascade() read"""
+        if not self._mind_on:
+            return self.registered_real_A
+        for_t, self._mind_handle = ops.fork(self.registered_real_A, 2)
+        return for_t
+
     def forward(self):
         if not self._batched:
             # the reference's own order (models/nemar_model.py:161-176)
@@ -500,7 +532,7 @@ class NEMARModel(BaseModel):
                 warped, reg_term = self.netR(self.real_A, self.real_B, apply_on=[self.real_A, self.fake_B])
             self.stn_reg_term = reg_term
             self.registered_real_A = warped[0]
-            self.fake_TR_B = self.netT(self.registered_real_A)     # registration first, then translation
+            self.fake_TR_B = self.netT(self._registered_for_netT())     # registration first, then translation
             self.fake_RT_B = warped[1]                             # translation first, then registration
         else:
             # Same graph, evaluated with T's two applications as ONE batch: the deformation depends on (a, b) only, so
@@ -514,7 +546,7 @@ class NEMARModel(BaseModel):
             self.registered_real_A = self.netR.warp(f_a, [self.real_A])[0]
             # (only the second half is differentiated: the stem's data gradient runs on it alone)
             with ops.norm_segments(2):
-                both = self.netT(ops.grad_from(ops.cat_batch([self.real_A, self.registered_real_A]), n))
+                both = self.netT(ops.grad_from(ops.cat_batch([self.real_A, self._registered_for_netT()]), n))
             self.fake_B, self.fake_TR_B = ops.split_batch(both, 2)
             self.fake_RT_B = self.netR.warp(f_b, [self.fake_B])[0]
             self.stn_reg_term = self.netR.regularization(f_reg, self.registered_real_A)
@@ -639,6 +671,15 @@ class NEMARModel(BaseModel):
             roots += lncc
             grads += [self._one] * 2
             total += [(t, 1.0) for t in lncc]
+        if self._mind_on:
+            # one more root: registered_real_A against real_B, descriptor against descriptor; it reaches netR through the warp and
+            # neither netT nor netD.  The weight is the kernel's factor
+            mind = ops.mind_loss(self._mind_handle, self.real_B.detach(), self._mind_patch, self._mind_dil, self._mind_eps, factor=self._lambda_mind)
+            self._mind_handle = None
+            self.loss_MIND_R = _LazyLoss([(mind, 1.0)])
+            roots.append(mind)
+            grads.append(self._one)
+            total.append((mind, 1.0))
         torch.autograd.backward(roots, grads)
         return _LazyLoss(total)
 

@@ -2284,6 +2284,46 @@ def local_ncc(x, y, win=9, eps=1e-5, factor=1.0, return_map=False):
     return _LocalNCC.apply(x, y, int(win), float(eps), float(factor), bool(return_map))
 
 
+class _MindLoss(Function):
+    @staticmethod
+    def forward(ctx, x, y, patch, dil, eps, factor, want_map):
+        x, y = _c(x), _c(y)
+        N, Cx, H, W = x.shape
+        Cy = y.shape[1]
+        loss = torch.empty((1,), dtype=torch.float32, device=x.device)
+        dm = torch.empty((N, 1, H, W), dtype=torch.float32, device=x.device) if want_map else None
+        wsb = Q.mind_loss_workspace(N, H, W, patch, dil)
+        ws = _workspace(wsb, x.device)
+        L.mind_loss_fwd(_p(x), Cx, _p(y), Cy, patch, dil, eps, factor, _p(loss), 0, _p(dm), _p(ws), wsb, N, H, W, _stream())
+        ctx.save_for_backward(x, y)
+        ctx.cfg = (patch, dil, eps, factor)
+        if not want_map:
+            return loss.reshape(())
+        ctx.mark_non_differentiable(dm)
+        return loss.reshape(()), dm
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _g_map=None):
+        x, y = ctx.saved_tensors
+        patch, dil, eps, factor = ctx.cfg
+        N, Cx, H, W = x.shape
+        gx = torch.empty_like(x)
+        gy = torch.empty_like(y) if ctx.needs_input_grad[1] else None
+        L.mind_loss_bwd(_p(x), Cx, _p(y), y.shape[1], patch, dil, eps, _p(_c(g)), factor, _p(gx), _p(gy), 0, N, H, W, _stream())
+        return gx, gy, None, None, None, None, None
+
+
+def mind_loss(x, y, patch=3, dilation=2, eps=1e-5, factor=1.0, return_map=False):
+    """factor * (mean over all pixels of dm), dm the squared distance of the MIND descriptors of x [N,Cx,H,W] and y [N,Cy,H,W] (two
+    modalities; each enters through its channel mean; nemar_mind_loss_fwd / _bwd; patch 3 or 5, dilation 1 or 2, no max-normalisation)
+    — a 0-dim device tensor with a gradient towards x, and towards y when y.requires_grad.  With return_map also the dm map
+    [N,1,H,W], no gradient.  No sync."""
+    if x.dim() != 4 or y.dim() != 4 or x.shape[0] != y.shape[0] or x.shape[2:] != y.shape[2:]:
+        raise ValueError("mind_loss: images %s and %s, expected [N,Cx,H,W] and [N,Cy,H,W] of one N, H and W" % (tuple(x.shape), tuple(y.shape)))
+    return _MindLoss.apply(x, y, int(patch), int(dilation), float(eps), float(factor), bool(return_map))
+
+
 def _svf_scales(steps, sign):
     """the scale each squaring step carries: sign / 2^K on the first, 1 on the others"""
     return [float(sign) / float(1 << steps)] + [1.0] * (steps - 1)
