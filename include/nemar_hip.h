@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 616 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 617 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -662,6 +662,30 @@ int nemar_registration_error(const float* pred, int grid_mode, const float* g, f
 #define NEMAR_SAMPLE_NEAREST 1
 int nemar_warp_resampled_fwd(const float* in, const float* pred, int grid_mode, int sample_mode, float* out,
                              int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* stream);
+
+/* The gradient of that pass towards the prediction (csrc/register.hip: the adjoint of nemar_warp_resampled_fwd with respect to `pred`,
+ * NEMAR_SAMPLE_BILINEAR only; not in the reference, which never warps at another size) — what refining a registration on its own pair
+ * at the pair's native size needs.  img [N,C,Hs,Ws] and pred are the forward's operands, gout [N,C,Ho,Wo] the gradient of its output.
+ * For sample n and output pixel (h,w), with (gx,gy) the coordinate the forward computes, a, b, c, d the four texels of channel ch it
+ * blends (0 outside the image) and tx, ty the fractions of the position, ex = 1 - tx, ey = 1 - ty:
+ *   dvx(n,h,w) = (Ws/2) sum_ch gout[n,ch,h,w] ((b - a) ey + (d - c) ty),   dvy(n,h,w) = (Hs/2) sum_ch gout[n,ch,h,w] ((c - a) ex + (d - b) tx)
+ * in the expression order of nemar_grid_sample_bwd's grid gradient, and exactly 0 where gx or gy is not finite.
+ *   NEMAR_GRID_UNET, (hf,wf) != (Ho,Wo)   gpred[n,0,j,i] = sum_{h,w} Wy_j(h) Wx_i(w) dvx(n,h,w), plane 1 with dvy: Wx_i(w) the weight the
+ *                                         resize gives field column i at output column w (both taps where they coincide at the border),
+ *                                         the exact adjoint of the forward's interpolation;
+ *   NEMAR_GRID_UNET, equal sizes          gpred = dv: bit for bit nemar_grid_sample_bwd's grid gradient at a source of the output's size;
+ *   NEMAR_GRID_AFFINE                     gpred[n,0..2] = sum dvx (xb, yb, 1), gpred[n,3..5] = sum dvy (xb, yb, 1), (xb, yb) affine_grid's base
+ *                                         coordinates at (Ho,Wo); hf, wf are ignored.
+ * accumulate = 1 adds to gpred (several images warped by one prediction share one gradient); 0 writes every element of gpred [N,2,hf,wf]
+ * or [N,6]: no zero-fill is expected.  Every sum is a gather in a fixed order — per-tile records in the workspace, merged by one thread
+ * per element: no atomics, bitwise repeatable, no host synchronisation.  No gradient towards img.  Pointers need 4-byte alignment only.
+ * NEMAR_EINVAL, with nothing launched and gpred untouched: a null pointer (ws may be NULL where the query is 0: UNET at equal sizes); a
+ * non-positive size; grid_mode other than UNET or AFFINE; N > 65535; Ho or Wo of 2^23 or more; ws_bytes below nemar_warp_resampled_bwd_workspace(); gpred equal
+ * to pred; a UNet field being DOWN-sampled (hf > Ho or wf > Wo): the forward serves it by an unstaged global-memory route that has no
+ * counterpart here — refinement, which optimises a prediction at the network's size against a larger pair, never needs it. */
+size_t nemar_warp_resampled_bwd_workspace(int grid_mode, int N, int hf, int wf, int Ho, int Wo);
+int nemar_warp_resampled_bwd(const float* img, const float* pred, int grid_mode, const float* gout, float* gpred, int accumulate,
+                             int N, int C, int Hs, int Ws, int hf, int wf, int Ho, int Wo, void* ws, size_t ws_bytes, void* stream);
 
 /* Scoring a registration of real data (csrc/score.hip; not in the reference, which has no evaluation code): segmentation overlap and
  * annotated-point distances, both read off the transformation exactly as nemar_warp_resampled_fwd applies it.  pred, grid_mode, hf and

@@ -121,6 +121,8 @@ SIGNATURES = {
     "nemar_registration_error_workspace": (_sz, [_i, _i, _i]),
     "nemar_registration_error": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_warp_resampled_fwd": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "nemar_warp_resampled_bwd_workspace": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "nemar_warp_resampled_bwd": (_i, [_vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "nemar_label_overlap": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_map_points": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_compose_pred": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

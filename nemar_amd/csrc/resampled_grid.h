@@ -95,6 +95,13 @@ struct FieldPatch {
     int px0, py0;      // the patch's first texel in the field
     bool staged;       // the taps fit the LDS patch (the same in every lane of the workgroup); otherwise they are read from global memory
 };
+// one axis of it: the texels [first, first + count) that the `tile` output pixels from d0 on (cut at n_out) tap in a field of n_in.
+// The one statement of the patch geometry: PredView::stage fills it, register.hip's backward reduces into it and finds it again
+struct PatchSpan { int first, count; };
+__device__ __forceinline__ PatchSpan patch_span(int d0, int tile, int n_in, int n_out, float scale) {
+    const Tap1D ta = tap1d(d0, n_in, scale), tb = tap1d(min(d0 + tile, n_out) - 1, n_in, scale);
+    return PatchSpan{ta.i0, tb.i1 - ta.i0 + 1};
+}
 
 // One prediction as one sample of one launch reads it: everything that is fixed for the launch and the sample.  Built inside the kernel
 // from its scalar arguments (pred_view) and indexed with constants only, so that theta and the sizes stay in scalar registers.
@@ -112,10 +119,9 @@ struct PredView {
     // without RESAMPLE
     __device__ __forceinline__ FieldPatch stage(float* patch, int x0, int y0, int tid) const {
         if (!RESAMPLE) return FieldPatch{0, 0, false};
-        const Tap1D ta = tap1d(x0, wf, sw), tb = tap1d(min(x0 + RT_W, Wo) - 1, wf, sw);
-        const Tap1D tc = tap1d(y0, hf, sh), td = tap1d(min(y0 + RT_H, Ho) - 1, hf, sh);
-        const int pw = tb.i1 - ta.i0 + 1, ph = td.i1 - tc.i0 + 1;
-        const FieldPatch fp{ta.i0, tc.i0, pw <= RT_PW && ph <= RT_PH};
+        const PatchSpan sx = patch_span(x0, RT_W, wf, Wo, sw), sy = patch_span(y0, RT_H, hf, Ho, sh);
+        const int pw = sx.count, ph = sy.count;
+        const FieldPatch fp{sx.first, sy.first, pw <= RT_PW && ph <= RT_PH};
         if (fp.staged) {
             for (int e = tid; e < 2 * ph * RT_PW; e += RT_THREADS) {
                 const int cr = e / RT_PW, rx = e - cr * RT_PW;      // cr: channel-major row of the patch

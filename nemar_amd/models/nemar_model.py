@@ -461,6 +461,85 @@ class NEMARModel(BaseModel):
                 out['inverse_offsets'] = inv[0]
         return out
 
+    REFINE_TERMS = ('mind', 'lncc', 'l1')
+    REFINE_LR = 3e-3                   # normalised units per Adam step (0.38 px of a 256-wide image) and the weight of the smoothness
+    REFINE_LAMBDA_SMOOTH = 1.0         # term: the best pair of tools/refine_record.py's sweep (tools/profiles/refine.txt)
+
+    def refine(self, full_A, full_B, steps, lr=None, term='mind', lambda_smooth=None, lambda_fold=0.0, fold_margin=0.0, **term_options):
+        """Test-time refinement ("instance optimisation"): `steps` Adam steps on THIS pair at its native size, starting from the last
+        prediction — the network's, or the composite after cascade().  The parameter is a fresh leaf at the network's size: the offsets
+        [N,2,h,w], the VELOCITY where netR was built with --stn_integrate K > 0 (the prediction inside the loop is its exponential, so
+        the result stays diffeomorphic and keeps its inverse_prediction()), or dtheta [N,6].  No network weight receives a gradient or
+        is read after the start.  Each step: full_A (for 'l1': netT(full_A), computed once) warped at full_B's size by the prediction
+        with a gradient towards it (netR.apply(..., grad=True): nemar_warp_resampled_bwd), the image term against full_B — 'mind'
+        (ops.mind_loss; across modalities, no generator pass), 'lncc' (ops.local_ncc) or 'l1' (ops.l1_loss; ValueError when netT
+        cannot run at full_A's size); term_options go to that op — plus, for a UNet STN, lambda_smooth * ops.smoothness(parameter) and
+        lambda_fold * ops.fold_penalty(prediction, fold_margin); then one nemar_adam_step (betas 0.9 / 0.999) on four plain buffers.
+        No host synchronisation.  Returns {'objective': float32 [steps + 1] on the device — before, and after each step — and 'offsets':
+        the refined prediction}, and installs it (and the refined velocity) as netR's last prediction: a following register() warps and
+        scores with it."""
+        steps = int(steps)
+        if steps < 0:
+            raise ValueError('refine: %d steps' % steps)
+        if term not in self.REFINE_TERMS:
+            raise ValueError('refine: term %r is not one of %s' % (term, self.REFINE_TERMS))
+        last = self.netR.last_prediction()
+        if last is None:
+            raise RuntimeError('refine: no forward pass yet')
+        mode = last[1]
+        lr = self.REFINE_LR if lr is None else float(lr)
+        lambda_smooth = self.REFINE_LAMBDA_SMOOTH if lambda_smooth is None else float(lambda_smooth)
+        K = getattr(self.netR, 'integrate', 0) if mode == ops.GRID_UNET else 0
+        velocity = getattr(self.netR, 'last_velocity', None) if K > 0 else None
+        with torch.no_grad():
+            full_A = full_A.to(self.device, dtype=torch.float32).contiguous()
+            full_B = full_B.to(self.device, dtype=torch.float32).contiguous()
+            if full_A.size(0) != last[0].size(0) or full_B.size(0) != last[0].size(0):
+                raise ValueError('refine: %d / %d images for a prediction of %d pairs' % (full_A.size(0), full_B.size(0), last[0].size(0)))
+            moving = full_A
+            if term == 'l1':
+                if not self._netT_runs_at(full_A.size(2), full_A.size(3)):
+                    raise ValueError("refine: term 'l1' needs netT(full_A), and netT (%s) cannot run at %d x %d"
+                                     % (self.opt.netG, full_A.size(2), full_A.size(3)))
+                moving = self.netT(full_A).contiguous()
+            start = last[0] if velocity is None else velocity
+            param = start.detach().clone().contiguous().requires_grad_(True)
+        image_term = {'mind': ops.mind_loss, 'lncc': ops.local_ncc, 'l1': ops.l1_loss}[term]
+        out_hw = tuple(full_B.shape[2:])
+        m, v = torch.zeros_like(param), torch.zeros_like(param)
+        objective = torch.empty((steps + 1,), dtype=torch.float32, device=self.device)
+        st = ops._stream
+
+        def prediction():
+            return self.netR._resized(ops.integrate_velocity(param, K)) if velocity is not None else param
+
+        def total(pred):
+            warped = self.netR.apply((pred, mode), [moving], out_hw=out_hw, grad=True)[0]
+            loss = image_term(warped, full_B, **term_options)
+            if mode == ops.GRID_UNET:
+                if lambda_smooth:
+                    loss = loss + ops.smoothness(param, None, 0.0, lambda_smooth)
+                if lambda_fold:
+                    loss = loss + ops.fold_penalty(pred, fold_margin, lambda_fold)
+            return loss
+
+        for k in range(steps):
+            param.grad = None
+            loss = total(prediction())
+            objective[k].copy_(loss.detach())
+            loss.backward()
+            ops.L.adam_step(ops._p(param), ops._p(param.grad.contiguous()), ops._p(m), ops._p(v), param.numel(), lr, 0.9, 0.999, 1e-8, k + 1, st())
+        with torch.no_grad():
+            pred = prediction().detach()
+            objective[steps].copy_(total(pred))
+            param.grad = None
+            refined = param.detach()
+            if mode == ops.GRID_UNET:
+                self.netR.set_refined(pred, refined if velocity is not None else None)
+            else:
+                self.netR.last_dtheta = refined
+        return {'objective': objective, 'offsets': pred}
+
     def _netT_runs_at(self, h, w):
         """netT is fully convolutional, but its strided levels must divide the size: two for the ResNet generators (a transposed
         convolution doubles what a stride-2 convolution halved only for even sizes), `num_downs` for the U-Nets (their skips concatenate)"""

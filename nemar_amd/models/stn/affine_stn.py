@@ -84,11 +84,11 @@ class AffineSTN(nn.Module):
     def warp(self, field, imgs):
         return ops.warp_affine(field, list(imgs))
 
-    def apply(self, field, imgs, out_hw=None, sample='bilinear'):
+    def apply(self, field, imgs, out_hw=None, sample='bilinear', grad=False):
         """The prediction applied at ANY resolution, for inference: `field` is what predict() returned or last_prediction(); each image
         is sampled at out_hw (default: its own size) on affine_grid(theta) of that size (ops.warp_resampled).  sample='nearest' for
-        label maps.  No autograd."""
-        return ops.warp_resampled(prediction_tensor(field), ops.GRID_AFFINE, list(imgs), out_hw, sample)
+        label maps.  No autograd — unless grad=True: the same values with a gradient towards the prediction (refinement on the pair)."""
+        return ops.warp_resampled(prediction_tensor(field), ops.GRID_AFFINE, list(imgs), out_hw, sample, grad)
 
     def overlap(self, field, labels_moving, labels_fixed, num_classes):
         """Per-class overlap counts [N,K,3] (inter, moving, fixed) of labels_moving warped by the prediction — what

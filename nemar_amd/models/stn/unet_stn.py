@@ -170,11 +170,18 @@ class UnetSTN(nn.Module):
     def warp(self, field, imgs):
         return ops.warp_unet(field[1], list(imgs))
 
-    def apply(self, field, imgs, out_hw=None, sample='bilinear'):
+    def apply(self, field, imgs, out_hw=None, sample='bilinear', grad=False):
         """The prediction applied at ANY resolution, for inference: `field` is what predict() returned or last_prediction() (the offsets
         at the network's size, already past the reference's low-resolution branch); each image is sampled at out_hw (default: its own
-        size) with the field resized inside the warp kernel (ops.warp_resampled).  sample='nearest' for label maps.  No autograd."""
-        return ops.warp_resampled(prediction_tensor(field), ops.GRID_UNET, list(imgs), out_hw, sample)
+        size) with the field resized inside the warp kernel (ops.warp_resampled).  sample='nearest' for label maps.  No autograd —
+        unless grad=True: the same values with a gradient towards the prediction (refinement on the pair)."""
+        return ops.warp_resampled(prediction_tensor(field), ops.GRID_UNET, list(imgs), out_hw, sample, grad)
+
+    def set_refined(self, offsets, velocity=None):
+        """what last_prediction() — and, with a velocity, inverse_prediction() — return from now on: a prediction refined on its own
+        pair (NEMARModel.refine).  The velocity is the one `offsets` was integrated from."""
+        self.last_offsets = offsets.detach()
+        self.last_velocity = None if velocity is None else velocity.detach()
 
     def overlap(self, field, labels_moving, labels_fixed, num_classes):
         """Per-class overlap counts [N,K,3] (inter, moving, fixed) of labels_moving warped by the prediction — what

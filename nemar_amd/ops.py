@@ -1687,15 +1687,62 @@ def grid_sample(img, grid):
 SAMPLE_MODES = {"bilinear": 0, "nearest": 1}
 
 
-def warp_resampled(pred, grid_mode, imgs, out_hw, sample='bilinear'):
+class _WarpResampled(Function):
+    """warp_resampled(grad=True): the same nemar_warp_resampled_fwd launches, and nemar_warp_resampled_bwd once per image — accumulating
+    from the second — as the gradient towards pred.  The images are constants."""
+
+    @staticmethod
+    def forward(ctx, pred, grid_mode, out_hw, *imgs):
+        pred = _c(pred)
+        N = pred.shape[0]
+        hf, wf = (int(pred.shape[2]), int(pred.shape[3])) if grid_mode == GRID_UNET else (0, 0)
+        outs, sizes, st = [], [], _stream()
+        for img in imgs:
+            _, C, Hs, Ws = img.shape
+            Ho, Wo = (Hs, Ws) if out_hw is None else out_hw
+            out = torch.empty((N, C, Ho, Wo), dtype=torch.float32, device=img.device)
+            L.warp_resampled_fwd(_p(img), _p(pred), grid_mode, SAMPLE_MODES['bilinear'], _p(out), N, C, Hs, Ws, hf, wf, Ho, Wo, st)
+            outs.append(out)
+            sizes.append((Ho, Wo))
+        ctx.save_for_backward(pred, *imgs)
+        ctx.cfg = (grid_mode, hf, wf, sizes)
+        return tuple(outs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *gouts):
+        pred, *imgs = ctx.saved_tensors
+        grid_mode, hf, wf, sizes = ctx.cfg
+        N = pred.shape[0]
+        gpred, st, done = torch.empty_like(pred), _stream(), 0
+        for img, gout, (Ho, Wo) in zip(imgs, gouts, sizes):
+            if gout is None:
+                continue
+            _, C, Hs, Ws = img.shape
+            wsb = Q.warp_resampled_bwd_workspace(grid_mode, N, hf, wf, Ho, Wo)
+            ws = _workspace(wsb, pred.device)
+            L.warp_resampled_bwd(_p(img), _p(pred), grid_mode, _p(_c(gout)), _p(gpred), 1 if done else 0, N, C, Hs, Ws, hf, wf, Ho, Wo,
+                                 _p(ws), wsb, st)
+            done += 1
+        if not done:
+            gpred.zero_()
+        return (gpred, None, None) + (None,) * len(imgs)
+
+
+def warp_resampled(pred, grid_mode, imgs, out_hw, sample='bilinear', grad=False):
     """The STN's prediction applied at another resolution (nemar_warp_resampled_fwd): pred = offsets [N,2,hf,wf] (GRID_UNET; resized
     bilinearly to out_hw inside the kernel, never written) or dtheta [N,6] (GRID_AFFINE); every image [N,C,Hs,Ws] of `imgs` is sampled
     at out_hw = (Ho, Wo) — or at its own size where out_hw is None — with F.grid_sample's 'bilinear' or 'nearest' (label maps) rule and
-    zero padding.  Returns the list of warped images.  An inference read-out like registration_error: inputs are detached, no autograd."""
+    zero padding.  Returns the list of warped images.  An inference read-out like registration_error: inputs are detached, no autograd.
+    grad=True ('bilinear' only; a field being down-sampled is a ValueError): the same launches and so the same bits, but the returned
+    tensors carry ONE autograd node whose backward is nemar_warp_resampled_bwd — the gradient towards pred only: the images are
+    still detached (refinement on the pair, NEMARModel.refine)."""
     if sample not in SAMPLE_MODES:
         raise ValueError("warp_resampled: sample %r is not one of %s" % (sample, sorted(SAMPLE_MODES)))
     if grid_mode not in (GRID_UNET, GRID_AFFINE):
         raise ValueError("warp_resampled: grid_mode %r (GRID_UNET or GRID_AFFINE)" % (grid_mode,))
+    if grad:
+        return _warp_resampled_grad(pred, grid_mode, imgs, out_hw, sample)
     pred = _c(pred.detach())
     N = pred.shape[0]
     if not ((pred.dim() == 4 and pred.shape[1] == 2) if grid_mode == GRID_UNET else tuple(pred.shape) == (N, 6)):
@@ -1712,6 +1759,25 @@ def warp_resampled(pred, grid_mode, imgs, out_hw, sample='bilinear'):
         L.warp_resampled_fwd(_p(img), _p(pred), grid_mode, SAMPLE_MODES[sample], _p(out), N, C, Hs, Ws, hf, wf, Ho, Wo, st)
         outs.append(out)
     return outs
+
+
+def _warp_resampled_grad(pred, grid_mode, imgs, out_hw, sample):
+    """warp_resampled's differentiable form: every refusal before any launch"""
+    if sample != 'bilinear':
+        raise ValueError("warp_resampled: grad=True differentiates bilinear sampling only, not %r" % (sample,))
+    N = pred.shape[0]
+    if not ((pred.dim() == 4 and pred.shape[1] == 2) if grid_mode == GRID_UNET else tuple(pred.shape) == (N, 6)):
+        raise ValueError("warp_resampled: prediction %s, expected [N,2,hf,wf] offsets or [N,6] dtheta" % (tuple(pred.shape),))
+    out_hw = None if out_hw is None else (int(out_hw[0]), int(out_hw[1]))
+    imgs = [_c(img.detach()) for img in imgs]
+    for img in imgs:
+        if img.dim() != 4 or img.shape[0] != N:
+            raise ValueError("warp_resampled: image %s for a prediction of %d samples" % (tuple(img.shape), N))
+        Ho, Wo = tuple(img.shape[2:]) if out_hw is None else out_hw
+        if grid_mode == GRID_UNET and (pred.shape[2] > Ho or pred.shape[3] > Wo):
+            raise ValueError("warp_resampled: grad=True with a field %s being down-sampled to %s (no backward for that route)"
+                             % (tuple(pred.shape[2:]), (Ho, Wo)))
+    return list(_WarpResampled.apply(pred, int(grid_mode), out_hw, *imgs))
 
 
 def _prediction(what, pred, grid_mode):

@@ -153,5 +153,13 @@ class TestOptions(BaseOptions):
         # python -m nemar_amd.register: registered_B.npy and inverse_offsets.npy, B warped onto A by the inverse prediction
         # (NEMARModel.register(inverse=True); needs --stn_integrate K > 0).  SUPPRESS: absent from an option set that does not ask for it
         a('--inverse', action='store_true', default=argparse.SUPPRESS)
+        # python -m nemar_amd.register: --refine N Adam steps on every batch's own pairs at their native size, from the network's
+        # prediction (NEMARModel.refine; refine.json, offsets_before_refine.npy); the image term, the step size and the weights of the
+        # regularisers — absent = NEMARModel.refine's defaults.  SUPPRESS as above
+        a('--refine', type=int, default=argparse.SUPPRESS)
+        a('--refine_term', choices=('mind', 'lncc', 'l1'), default=argparse.SUPPRESS)
+        a('--refine_lr', type=float, default=argparse.SUPPRESS)
+        a('--refine_lambda_smooth', type=float, default=argparse.SUPPRESS)
+        a('--refine_lambda_fold', type=float, default=argparse.SUPPRESS)
         self.isTrain = False
         return parser

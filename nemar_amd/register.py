@@ -50,8 +50,18 @@ Written under --results_dir/--name/:
     inverse_offsets.npy       only with --inverse: that prediction [M,2,h,w], exp(-v) of the velocity field the network predicted
                               (csrc/integrate.hip).  It inverts the integrated map in its true-identity convention; the slight zoom
                               of the warp's grid is not undone
+    refine.json               only with --refine N: every batch's prediction is refined on its own pairs at their native size before it
+                              is applied and scored — N Adam steps on the offsets (the velocity with --stn_integrate; dtheta) against
+                              --refine_term mind | lncc | l1 (default mind: across modalities, no generator pass) and the regularisers
+                              (--refine_lr, --refine_lambda_smooth, --refine_lambda_fold; NEMARModel.refine, csrc/register.hip's
+                              backward): the steps, the term and the objective before and after, the mean over the data set.  Every
+                              other file then holds the refined result ("before" in the score files stays the identity) — except
+                              the `per_pass` lists of regularity.json and similarity.json under --passes K > 1: they are taken
+                              while the network looks, BEFORE the refinement, so their last entry is the composite the refinement
+                              started from and differs from "after" and the file's own totals, which are the refined one's
+    offsets_before_refine.npy only with --refine N: what offsets.npy would have held without it
 and one summary line on stdout: pairs, sizes, the scores (with --regularity: folds in per cent and SDlogJ; with --similarity:
-MI before -> after; with --surface: HD95 before -> after), seconds."""
+MI before -> after; with --surface: HD95 before -> after; with --refine: the objective before -> after), seconds."""
 import json
 import os
 import time
@@ -181,6 +191,10 @@ def main(argv=None):
     raw_B = np.load(os.path.join(opt.dataroot, 'B.npy'), mmap_mode='r') if want_inverse else None
     reg_B, inv_offsets = [], []
     reg, reg_labels, offsets = [], [], []
+    refine_steps, refine_term = int(getattr(opt, 'refine', 0)), getattr(opt, 'refine_term', 'mind')
+    if refine_steps < 0:
+        raise SystemExit('--refine %d: a number of steps' % refine_steps)
+    offsets_before, objectives = [], []
     for i0 in range(0, M, opt.batch_size):
         idx = list(range(i0, min(M, i0 + opt.batch_size)))
         model.set_input(network_batch(pool_A, pool_B, idx, opt))
@@ -194,6 +208,12 @@ def main(argv=None):
         for k, pair in zip(sim_per_pass, sim_passes):
             k.append(pair)
         part = lambda t: None if t is None else t[idx[0]:idx[-1] + 1]
+        if refine_steps:
+            offsets_before.append(model.netR.last_prediction()[0].clone())
+            as_net = (lambda t: t * 2.0 - 1.0) if refine_term == 'l1' else (lambda t: t)      # (netT reads [-1, 1])
+            refined = model.refine(as_net(part(pool_A)), as_net(part(pool_B)), refine_steps, lr=getattr(opt, 'refine_lr', None), term=refine_term,
+                                   lambda_smooth=getattr(opt, 'refine_lambda_smooth', None), lambda_fold=getattr(opt, 'refine_lambda_fold', 0.0))
+            objectives.append(refined['objective'][[0, -1]] * len(idx))
         out = model.register(part(pool_A), part(pool_B), part(labels), translate=False,          # (fake_RT_B is not among the files this command writes)
                              labels_B=part(labels_B), landmarks_A=part(lm_A), landmarks_B=part(lm_B), num_classes=num_classes,
                              **(dict(regularity=True, jacobian_map=opt.jacobian_map) if want_reg else {}),
@@ -231,6 +251,11 @@ def main(argv=None):
         np.save(os.path.join(out_dir, 'registered_B.npy'), _like_input(torch.cat(reg_B), raw_B, True))
         np.save(os.path.join(out_dir, 'inverse_offsets.npy'), torch.cat(inv_offsets).cpu().numpy())
     told = ''
+    if refine_steps:
+        np.save(os.path.join(out_dir, 'offsets_before_refine.npy'), torch.cat(offsets_before).cpu().numpy())
+        before, after = (torch.stack(objectives).sum(0) / M).tolist()          # the batches' objectives are means over their pairs
+        with open(os.path.join(out_dir, 'refine.json'), 'w') as f:
+            json.dump({'steps': refine_steps, 'term': refine_term, 'objective_before': before, 'objective_after': after}, f, indent=1)
     if scored['overlap'] or scored['tre_px']:
         host = {k: torch.cat(v).cpu().numpy() if v else None for k, v in scored.items()}
         scores = score_summary(host['overlap_before'], host['overlap'], host['tre_before_px'], host['tre_px'])
@@ -269,6 +294,8 @@ def main(argv=None):
             np.save(os.path.join(out_dir, 'surface_dist2.npy'), torch.cat(surf['dist2']).cpu().numpy())
         hd95 = [surface[k]['mean']['hd95'] for k in ('before', 'after')]
         told += ', HD95 %s -> %s px' % tuple('n/a' if v is None else '%.3f' % v for v in hd95)
+    if refine_steps:
+        told += ', refined %d steps: objective %.5f -> %.5f' % (refine_steps, before, after)
     torch.cuda.synchronize()
     print('registered %d pairs: %dx%d images with the %s prediction made at %dx%d%s%s%s, %.2f s -> %s'
           % (M, pool_A.shape[2], pool_A.shape[3], opt.stn_type, opt.img_height, opt.img_width, '' if opt.passes == 1 else ' in %d passes' % opt.passes,
