@@ -32,7 +32,7 @@ extern "C" {
 #define NEMAR_EWORKSPACE (-3)
 
 /* library */
-int nemar_version(void);              /* major*10000 + minor*100 + patch; 617 = this header (0.4.x exported nemar_tune*) */
+int nemar_version(void);              /* major*10000 + minor*100 + patch; 618 = this header (0.4.x exported nemar_tune*) */
 const char* nemar_last_error(void);   /* thread-local message of the last failing call */
 
 /* ---- K9/K10/K11: sampling-grid generation fused into bilinear grid_sample ------------------------------
@@ -746,6 +746,39 @@ int nemar_map_points(const float* pts, const float* pred, int grid_mode, float* 
  * equal to an operand, img or out_field (the kernel gathers from them). */
 int nemar_compose_pred(const float* first, int first_mode, int h1, int w1, const float* second, int second_mode, int h2, int w2,
                        float* out_field, const float* img, float* out_img, int C, int N, int H, int W, void* stream);
+
+/* The gradient of nemar_compose_pred's out_field towards its two operands (csrc/compose.hip): what training a cascade with shared weights
+ * needs.  Training size only: a NEMAR_GRID_UNET operand is AT the composition size, (h,w) == (H,W) — a resampled one is NEMAR_EINVAL (the
+ * forward keeps accepting it); h and w of a NEMAR_GRID_AFFINE operand are ignored.  With out_c(x) = grid_at<M1>(first, p(x))_c - linspace_c(x),
+ * p(x) = ((g2 + 1) * size - 1) / 2 of second's coordinate g2 at x, and gout [N,2,H,W]:
+ *   gfirst, first UNET [N,2,H,W]   sum over x of w_k(p(x)) * gout_c(x) at the four texels the forward's bilinear taps read (source
+ *                                  coordinate (p + 0.5) - 0.5 clamped to [0, size-1]; weights l0x l0y, l1x l0y, l0x l1y, l1x l1y).  p is
+ *                                  anywhere, so this is a scatter: 64-bit fixed-point integer atomics into the zeroed leading bytes of the
+ *                                  workspace, each w * gout rounded to a multiple of 2^(e - FIX), 2^(e-1) <= max |gout| of the call < 2^e
+ *                                  (found on the device; e clamped at -80), FIX = min(40, 62 - ceil(log2(H W))) — the rule of
+ *                                  nemar_svf_step_bwd — then gfirst = (accumulate_first ? gfirst : 0) + sum, the sum rounded to fp32 first;
+ *   gfirst, first AFFINE [N,6]     sum over x of gout_x * (xb, yb, 1), gout_y * (xb, yb, 1), xb = (2 p.x + 1)/W - 1, yb = (2 p.y + 1)/H - 1:
+ *                                  one record per 64 x 16 tile, merged in a fixed order;
+ *   gp_a(x)                        sum_c gout_c(x) * d grid_at_c / d p_a.  First UNET: the identity's slope 2/(size-1) (0 for size 1) on
+ *                                  the diagonal plus the bilinear slope of first's 2 x 2 cell, which is zero along an axis whose source
+ *                                  coordinate was clamped (< 0 or > size-1).  First AFFINE: theta's 2 x 2 part times 2/W, 2/H;
+ *   gsecond, second UNET [N,2,H,W] (gp_x * W/2, gp_y * H/2) at the pixel itself: (accumulate_second ? gsecond : 0) + that, no atomics;
+ *   gsecond, second AFFINE [N,6]   sum over x of gp_x W/2 * (xb, yb, 1), gp_y H/2 * (xb, yb, 1) at the PIXEL's base coordinates
+ *                                  xb = (2w + 1)/W - 1, yb = (2h + 1)/H - 1: tile records and the same merge.
+ * A pixel whose position p is not finite contributes exactly 0 to both gradients.  Positions are clamped in float before the integer
+ * conversion: no input value indexes outside a plane.  gfirst or gsecond may be NULL (not both): that gradient is not computed, and the
+ * bits of the other do not depend on it.  Bitwise repeatable, no fp32 atomics, no host sync (capturable into a graph).
+ * Workspace: nemar_compose_pred_bwd_workspace() bytes, 8-byte aligned, whose first nemar_compose_pred_bwd_zeroed_bytes() (the accumulator
+ * of a UNET first; 0 for an AFFINE first) are zero on entry and left zero on return; the rest is scratch.
+ * NEMAR_EINVAL, nothing launched: first, second, gout or workspace NULL; gfirst and gsecond both NULL; a given pointer not 4-byte aligned
+ * (workspace: 8-byte); a non-positive N, H or W; N > 65535; H*W >= 2^31 (a UNET operand: >= 2^30); H > 16 * 65535; a mode that is not
+ * NEMAR_GRID_UNET or NEMAR_GRID_AFFINE; a UNET operand with (h,w) != (H,W); gfirst or gsecond equal to first, second, gout or each other;
+ * ws_bytes < nemar_compose_pred_bwd_workspace(). */
+size_t nemar_compose_pred_bwd_workspace(int first_mode, int second_mode, int N, int H, int W);
+size_t nemar_compose_pred_bwd_zeroed_bytes(int first_mode, int second_mode, int N, int H, int W);
+int nemar_compose_pred_bwd(const float* first, int first_mode, int h1, int w1, const float* second, int second_mode, int h2, int w2,
+                           const float* gout, float* gfirst, int accumulate_first, float* gsecond, int accumulate_second, void* workspace,
+                           size_t ws_bytes, int N, int H, int W, void* stream);
 
 /* Regularity of a registration (csrc/regularity.hip; not in the reference, which has no evaluation code): the Jacobian determinant of
  * the transformation a prediction describes, as a map and as fold / log-Jacobian statistics, at the size the images are registered at,

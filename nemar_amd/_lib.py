@@ -126,6 +126,9 @@ SIGNATURES = {
     "nemar_label_overlap": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_map_points": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "nemar_compose_pred": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "nemar_compose_pred_bwd_workspace": (_sz, [_i, _i, _i, _i, _i]),
+    "nemar_compose_pred_bwd_zeroed_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "nemar_compose_pred_bwd": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _sz, _i, _i, _i, _vp]),
     "nemar_jacobian_stats_workspace": (_sz, [_i, _i, _i]),
     "nemar_jacobian_stats": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
     "nemar_joint_histogram_workspace": (_sz, [_i, _i, _i]),

@@ -49,7 +49,7 @@ size_t nemar_lds_bytes(const void* kernel, size_t need, bool claim) {
 #endif
 }
 
-#define NEMAR_HIP_VERSION 617  // major*10000 + minor*100 + patch  (0.6.17: nemar_warp_resampled_bwd; 0.6.16: nemar_mind_loss_*; 0.6.15: nemar_dice_*; 0.6.14: nemar_epe_loss_*; 0.6.13: nemar_local_ncc_*; 0.6.12: nemar_surface_distance; 0.6.11: nemar_svf_step_*; 0.6.10: nemar_fold_penalty_*; 0.6.9: nemar_joint_histogram; 0.6.8: nemar_jacobian_stats; 0.6.7: nemar_compose_pred; 0.6.6: nemar_label_overlap, nemar_map_points; 0.6.5: nemar_warp_resampled_fwd; 0.6.4: nemar_deform_field, nemar_crop_flip_deform_normalize, nemar_registration_error; 0.6.3: nemar_batchnorm_*; 0.6.2: nemar_concat_pieces, nemar_add2; 0.6.1: nemar_set_max_words_lazy; 0.6.0: round 6 — producer-written operand planes for all three calls of the
+#define NEMAR_HIP_VERSION 618  // major*10000 + minor*100 + patch  (0.6.18: nemar_compose_pred_bwd; 0.6.17: nemar_warp_resampled_bwd; 0.6.16: nemar_mind_loss_*; 0.6.15: nemar_dice_*; 0.6.14: nemar_epe_loss_*; 0.6.13: nemar_local_ncc_*; 0.6.12: nemar_surface_distance; 0.6.11: nemar_svf_step_*; 0.6.10: nemar_fold_penalty_*; 0.6.9: nemar_joint_histogram; 0.6.8: nemar_jacobian_stats; 0.6.7: nemar_compose_pred; 0.6.6: nemar_label_overlap, nemar_map_points; 0.6.5: nemar_warp_resampled_fwd; 0.6.4: nemar_deform_field, nemar_crop_flip_deform_normalize, nemar_registration_error; 0.6.3: nemar_batchnorm_*; 0.6.2: nemar_concat_pieces, nemar_add2; 0.6.1: nemar_set_max_words_lazy; 0.6.0: round 6 — producer-written operand planes for all three calls of the
                                // wide layers, fused skip-gradient add / max words in the data gradient's epilogue; 0.5.0: round 5 — no nemar_tune* in the product library: the measurement
                                // switches are constants there and live in libnemar_hip_ab.so (-DNEMAR_AB, include/nemar_hip_ab.h);
                                // 0.4.0: side inputs per call only, weight-pack plans, nemar_store_words, 7x7 layers on the 16-bit pipe)

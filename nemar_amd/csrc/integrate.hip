@@ -27,12 +27,10 @@
 // a plane lands on one border texel the 64-bit sum cannot overflow.  Nothing synchronises with the host: capturable into the step graph.
 // Plain fp32 apart from that accumulator, built without contraction like its neighbours.
 #include "common.h"
+#include "fixed_scatter.h"
 #include "pred_launch.h"
 
 namespace {
-
-constexpr int SVF_FIX_BITS = 40;
-constexpr int SVF_MAX_PARTIALS = 256;      // workgroups of svf_max_kernel = partial words in the workspace (one per thread of a consumer)
 
 // where pixel (h, w) with scaled displacement (a0, a1) samples: the top-left texel (x0, y0) of its 2 x 2 patch, the other corner clamped
 // into the plane (x1 == x0 at the last column: its weight is then 0), the fractional position, whether the raw position was clamped
@@ -86,31 +84,7 @@ __global__ __launch_bounds__(RT_THREADS) void svf_step_fwd_kernel(const float* _
 }
 
 // ---- backward ------------------------------------------------------------------------------------------------------------------
-// max over the call of the bit patterns of |gout| (a NaN counts as larger than every float: the scale then is the smallest one)
-__global__ __launch_bounds__(256) void svf_max_kernel(const float* __restrict__ gout, long long total, unsigned* __restrict__ partial) {
-    __shared__ unsigned red[4];
-    unsigned m = 0u;
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256)
-        m = max(m, __float_as_uint(gout[i]) & 0x7fffffffu);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = max(max(red[0], red[1]), max(red[2], red[3]));
-}
-
-// e with max |gout| < 2^e, from the partial words, in every thread of a 256-thread workgroup (clamped: 2^(fix - e) must be a float)
-__device__ __forceinline__ int svf_exponent(const unsigned* __restrict__ partial, int partials, unsigned* red) {
-    unsigned m = (int)threadIdx.x < partials ? partial[threadIdx.x] : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-    __syncthreads();
-    m = max(max(red[0], red[1]), max(red[2], red[3]));
-    return max((int)((m >> 23) & 255u) - 126, -80);
-}
-__device__ __forceinline__ float svf_pow2(int e) { return __uint_as_float((unsigned)(127 + e) << 23); }      // -126 <= e <= 127
-
+// (the scale of the fixed-point scatter — svf_max_kernel, svf_exponent, svf_pow2, svf_fix_bits — is in fixed_scatter.h)
 __global__ __launch_bounds__(RT_THREADS) void svf_scatter_kernel(const float* __restrict__ u, float s, const float* __restrict__ gout,
                                                                  long long* __restrict__ acc, const unsigned* __restrict__ partial,
                                                                  int partials, int fix, int H, int W) {
@@ -184,17 +158,6 @@ __global__ __launch_bounds__(RT_THREADS) void svf_fold_kernel(const float* __res
 bool svf_shape_ok(int N, int H, int W) {
     return N > 0 && H > 0 && W > 0 && N <= 65535 && (long long)H * W < (1ll << 31) && nemar_cdiv(H, RT_H) <= 65535;
 }
-int svf_partials(int N, int H, int W) {
-    const long long blocks = nemar_cdiv((long long)N * 2 * H * W, 1024);
-    return (int)(blocks < SVF_MAX_PARTIALS ? blocks : SVF_MAX_PARTIALS);
-}
-// fixed-point bits below 2^e: H W contributions of less than 2^(fix + 1) each stay below 2^63
-int svf_fix_bits(int H, int W) {
-    int lg = 0;
-    while ((1ll << lg) < (long long)H * W) ++lg;
-    return 62 - lg < SVF_FIX_BITS ? 62 - lg : SVF_FIX_BITS;
-}
-
 }  // namespace
 
 NEMAR_API int nemar_svf_step_fwd(const float* u, float scale, float* out, int N, int H, int W, void* stream) {

@@ -124,6 +124,11 @@ class NEMARModel(BaseModel):
                                 help='number of classes of the label-overlap term (default: --labels)')
             parser.add_argument('--dice_background', action='store_true', default=argparse.SUPPRESS,
                                 help='average the label-overlap term over class 0 too (default: the background is left out)')
+            # (MI355X build) train the cascade: netR looks at the pair K times with shared weights, the predictions composed into the one
+            # transformation every term acts on (UnetSTN.predict(passes=K), ops.compose_predictions(grad=True)).  Read like --lambda_fold
+            parser.add_argument('--train_passes', type=int, default=argparse.SUPPRESS,
+                                help='unet STN only: passes of the registration network per training step, 1 .. 8, composed into one '
+                                     'transformation and trained end to end (default 1: a single look)')
             parser.add_argument('--enable_tbvis', action='store_true',
                                 help='Enable tensorboard visualizer (default : False)')
             parser.add_argument('--multi_resolution', type=int, default=1,
@@ -146,6 +151,13 @@ class NEMARModel(BaseModel):
         if self._fold_on and opt.stn_type != 'unet':
             raise ValueError('--lambda_fold %g needs --stn_type unet: the %s STN has no fold term (theta\'s determinant is one number per '
                              'sample, not a field to regularise)' % (self._lambda_fold, opt.stn_type))
+        # the trained cascade: K looks of netR per training step, composed; only a dense field has a compose gradient at training size
+        self._train_passes = int(getattr(opt, 'train_passes', 1)) if self.isTrain else 1
+        if not 1 <= self._train_passes <= 8:
+            raise ValueError('--train_passes %d: the passes of a training step are 1 .. 8' % self._train_passes)
+        if self._train_passes > 1 and opt.stn_type != 'unet':
+            raise ValueError('--train_passes %d needs --stn_type unet: cascade training composes dense fields (the %s STN composes in '
+                             'closed form and is not trained that way)' % (self._train_passes, opt.stn_type))
         # the local NCC terms: two more image losses of the training step, any STN
         self._lambda_lncc, self._lncc_win = float(getattr(opt, 'lambda_lncc', 0.0)), int(getattr(opt, 'lncc_win', 9))
         self._lncc_on = bool(self.isTrain and self._lambda_lncc != 0.0)
@@ -316,7 +328,8 @@ class NEMARModel(BaseModel):
         that samples where the two would in sequence) and warps the ORIGINAL real_A by the composite — one interpolation however many
         passes, the UNet STN's in the composing launch itself.  Afterwards netR.last_prediction() is the composite, registered_real_A and
         fake_RT_B are warps by it and fake_TR_B = netT(registered_real_A), so register() and registration_error() work unchanged.
-        cascade(1) is test().  Inference only: no autograd, no regularisation term for the further passes.
+        cascade(1) is test().  Inference only: no autograd, no regularisation term for the further passes (training the cascade is
+        --train_passes K: UnetSTN.predict(passes=K)).
         With regularity=True returns a list of `passes` (counts, stats) pairs: netR.regularity of the accumulated transformation after
         each pass, at the network's size (composites are where folds appear); by default returns None, as before.
         With similarity=True returns a list of `passes` (counts, moments) pairs: netR.similarity of real_A under the accumulated
@@ -557,7 +570,9 @@ class NEMARModel(BaseModel):
         extra = int(self._epe_on) + int(self._dice_on)
         if extra:
             kw['extra'] = extra
-        out = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B), n_warps, **kw)
+        # (the cascade is a matter of the training step: test() and what builds on it look once)
+        looks = {'passes': self._train_passes} if self._train_passes > 1 and torch.is_grad_enabled() else {}
+        out = self.netR.fork_field(self.netR.predict(self.real_A, self.real_B, **looks), n_warps, **kw)
         more = list(out[-1]) if extra else []
         return (out[0], out[1], (out[2] if self._fold_on else None), (more.pop(0) if self._epe_on else None),
                 (more.pop(0) if self._dice_on else None))
@@ -601,8 +616,8 @@ class NEMARModel(BaseModel):
         if not self._batched:
             # the reference's own order (models/nemar_model.py:161-176)
             self.fake_B = self.netT(self.real_A)
-            if self._fold_on or self._epe_on or self._dice_on:
-                # netR.forward() piece by piece, with one more handle of the field for each further term
+            if self._fold_on or self._epe_on or self._dice_on or self._train_passes > 1:
+                # netR.forward() piece by piece, with one more handle of the field for each further term (or with several looks)
                 (f_warp,), f_reg, f_fold, f_epe, f_dice = self._fork_prediction(1)
                 warped = self.netR.warp(f_warp, [self.real_A, self.fake_B])
                 reg_term = self.netR.regularization(f_reg, warped[0])

@@ -164,8 +164,33 @@ class UnetSTN(nn.Module):
 
     # The forward pass in three pieces, so that a caller can evaluate the deformation once and warp several tensors at
     # different points of its own graph (NEMARModel runs T on [a, R(a)] as one batch): predict -> warp* -> regularization
-    def predict(self, img_a, img_b):
-        return self._deformation(img_a, img_b)
+    def predict(self, img_a, img_b, passes=1):
+        """passes = K > 1 (--train_passes; not in the reference): a recursive cascade with SHARED weights, trained end to end.  The
+        accumulated prediction starts as pass 1's field, taken where the warp reads it (after --stn_integrate and the low-resolution
+        resize); every further pass warps the ORIGINAL img_a by it (one interpolation, as NEMARModel.cascade does), predicts from (that
+        image, img_b) and composes the accumulated field with the new one (ops.compose_predictions(grad=True): both operands receive a
+        gradient, the accumulated one a second through the warp — two handles, ops.fork).  Returns (composite, composite): the warps,
+        the smoothness regulariser and the fold, EPE and Dice terms all act on the ONE transformation the warp reads — the regulariser
+        sees the composite, not each pass's own field (nor, under --stn_integrate, the velocities).  Afterwards last_offsets is the
+        detached composite, last_velocity None (a composite is the exponential of no single velocity) and last_pass_predictions the
+        list of the K detached per-pass fields.  passes = 1 is the single look: exactly the code path without the argument."""
+        passes = int(passes)
+        if passes == 1:
+            return self._deformation(img_a, img_b)
+        if not 1 <= passes <= 8:
+            raise ValueError('UnetSTN.predict: passes %d (1 .. 8)' % passes)
+        _, acc = self._deformation(img_a, img_b)
+        per_pass = [self.last_offsets]
+        for _ in range(passes - 1):
+            acc_warp, acc_comp = ops.fork(acc, 2)
+            moved = ops.warp_unet(acc_warp, [img_a])[0]
+            _, nxt = self._deformation(moved, img_b)
+            per_pass.append(self.last_offsets)
+            acc = ops.compose_predictions(acc_comp, ops.GRID_UNET, nxt, ops.GRID_UNET, (self.oh, self.ow), grad=True)
+        self.last_offsets = acc.detach()
+        self.last_velocity = None
+        self.last_pass_predictions = per_pass
+        return acc, acc
 
     def warp(self, field, imgs):
         return ops.warp_unet(field[1], list(imgs))
@@ -212,15 +237,16 @@ class UnetSTN(nn.Module):
         ops.similarity_summary turns them into mutual information, NCC, MSE and MAE.  Needs no annotation.  No autograd."""
         return ops.joint_histogram(prediction_tensor(field), ops.GRID_UNET, moving, fixed, bins, range_moving, range_fixed, moments)
 
-    def compose(self, first, second, image=None):
+    def compose(self, first, second, image=None, grad=False):
         """ONE prediction that samples where `first` and then `second` would in sequence — `second` was predicted from the pair `first`
         had already registered (a cascade pass), or `first` comes from an earlier run: the composite offsets [N,2,oh,ow] at the network's
         size (ops.compose_predictions), which apply(), overlap() and map_points() take like any prediction of this network.  Either
         operand may be a `(tensor, grid mode)` pair of another STN (an affine pre-registration).  With image [N,C,oh,ow] returns
         (offsets, image warped by them), from the same launch.  A zero field is the reference's slight zoom, not the identity, and
-        composing keeps it: compose(first, zeros) != first.  No autograd."""
+        composing keeps it: compose(first, zeros) != first.  No autograd — unless grad=True (no image then; a UNet operand at the
+        network's size): the same values with a gradient towards both operands (ops.compose_predictions)."""
         return ops.compose_predictions(prediction_tensor(first), prediction_mode(first, ops.GRID_UNET), prediction_tensor(second),
-                                       prediction_mode(second, ops.GRID_UNET), (self.oh, self.ow), image)
+                                       prediction_mode(second, ops.GRID_UNET), (self.oh, self.ow), image, grad)
 
     def set_last_prediction(self, offsets):
         """what last_prediction() returns from now on: a composite made outside the forward pass (NEMARModel.cascade)"""

@@ -1928,13 +1928,66 @@ def map_points(pred, grid_mode, pts, src_hw, out_hw):
     return out
 
 
-def compose_predictions(first, first_mode, second, second_mode, out_hw, image=None):
+class _ComposePredictions(Function):
+    """compose_predictions(grad=True): the same nemar_compose_pred launch, and nemar_compose_pred_bwd as the gradient towards the operands
+    that ask for one."""
+
+    @staticmethod
+    def forward(ctx, first, first_mode, second, second_mode, H, W):
+        first, second = _c(first), _c(second)
+        N = first.shape[0]
+        h1, w1 = (int(first.shape[2]), int(first.shape[3])) if first_mode == GRID_UNET else (0, 0)
+        h2, w2 = (int(second.shape[2]), int(second.shape[3])) if second_mode == GRID_UNET else (0, 0)
+        field = torch.empty((N, 2, H, W), dtype=torch.float32, device=first.device)
+        with _span('compose_pred'):
+            L.compose_pred(_p(first), first_mode, h1, w1, _p(second), second_mode, h2, w2, _p(field), None, None, 0, N, H, W, _stream())
+        ctx.save_for_backward(first, second)
+        ctx.cfg = (first_mode, h1, w1, second_mode, h2, w2, N, H, W)
+        return field
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gout):
+        first, second = ctx.saved_tensors
+        first_mode, h1, w1, second_mode, h2, w2, N, H, W = ctx.cfg
+        need_first, need_second = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        if not (need_first or need_second):
+            return None, None, None, None, None, None
+        gout = _c(gout)
+        gfirst = torch.empty_like(first) if need_first else None
+        gsecond = torch.empty_like(second) if need_second else None
+        wsb = Q.compose_pred_bwd_workspace(first_mode, second_mode, N, H, W)
+        ws = _zeroed_workspace(wsb, (gout.device, 'compose', first_mode, second_mode, N, H, W))      # leading part: all-zero in and out
+        with _span('compose_pred_bwd'):
+            L.compose_pred_bwd(_p(first), first_mode, h1, w1, _p(second), second_mode, h2, w2, _p(gout), _p(gfirst), 0, _p(gsecond), 0, _p(ws),
+                               wsb, N, H, W, _stream())
+        return gfirst, None, gsecond, None, None, None
+
+
+def compose_predictions(first, first_mode, second, second_mode, out_hw, image=None, grad=False):
     """ONE prediction that samples where two would in sequence (nemar_compose_pred): `first` is applied to the image first, `second` to
     the result — A2(x) = A(S1(S2(x))).  Each is offsets [N,2,h,w] (GRID_UNET; its own size, resized inside the kernel) or dtheta [N,6]
     (GRID_AFFINE).  Returns the composite, always a GRID_UNET offset field [N,2,H,W] at out_hw = (H, W), which warp_resampled,
     label_overlap and map_points read like any UNet prediction.  With image [N,C,H,W] returns (field, warped): the image warped
     bilinearly by the composite in the same launch, bit for bit warp_resampled(field, GRID_UNET, [image], None)[0].  A zero UNet
-    prediction is the reference's slight zoom, not the identity (that is GRID_AFFINE zeros [N,6]).  No autograd, no sync."""
+    prediction is the reference's slight zoom, not the identity (that is GRID_AFFINE zeros [N,6]).  No autograd, no sync.
+    grad=True (training a cascade): the same launch and so the same bits, but the field carries ONE autograd node whose backward is
+    nemar_compose_pred_bwd — towards the operands that require a gradient only.  A UNet operand must then be AT out_hw (a resampled
+    one is a ValueError), and `image` is a ValueError: the fused image output stays inference only, training warps with warp_unet."""
+    if grad:
+        if image is not None:
+            raise ValueError("compose_predictions: grad=True with image (the fused warp has no gradient: warp the composite with warp_unet)")
+        for what, pred, mode in (("first", first, first_mode), ("second", second, second_mode)):
+            if mode not in (GRID_UNET, GRID_AFFINE):
+                raise ValueError("compose_predictions: grid_mode %r (GRID_UNET or GRID_AFFINE)" % (mode,))
+            if not ((pred.dim() == 4 and pred.shape[1] == 2) if mode == GRID_UNET else tuple(pred.shape) == (pred.shape[0], 6)):
+                raise ValueError("compose_predictions: prediction %s, expected [N,2,hf,wf] offsets or [N,6] dtheta" % (tuple(pred.shape),))
+            if mode == GRID_UNET and tuple(pred.shape[2:]) != (int(out_hw[0]), int(out_hw[1])):
+                raise ValueError("compose_predictions: grad=True with the %s field %s resampled to %s (no backward: a UNet operand must be "
+                                 "at the composition size)" % (what, tuple(pred.shape[2:]), (int(out_hw[0]), int(out_hw[1]))))
+        if first.shape[0] != second.shape[0]:
+            raise ValueError("compose_predictions: predictions of %d and %d samples" % (first.shape[0], second.shape[0]))
+        return _ComposePredictions.apply(first, int(first_mode), second, int(second_mode), int(out_hw[0]), int(out_hw[1]))
     first, N, h1, w1 = _prediction("compose_predictions", first, first_mode)
     second, N2, h2, w2 = _prediction("compose_predictions", second, second_mode)
     if N2 != N:
